@@ -4,6 +4,14 @@
     python bench.py --gpus N --steps K --warmup W          (runs as typed: for N>1 without a launcher it starts its own N ranks,
                                                             one per GPU, as the reference does with mp.spawn, main.py:60-69;
                                                             under torch.distributed.run it takes the launcher's environment)
+    python bench.py ... --full                             (also the figures below: roofline, roofline_conv1d, the informational legs
+                                                            behind the timed region, cpu_baseline)
+    python bench.py ... --dump-outputs DIR                 (after the timed steps: the losses and results of the last timed step as
+                                                            DIR/losses.<name>.npy, DIR/results.<name>.npy, float32 / float64)
+
+A plain run sets up, warms up, times the K steps, writes its outputs when asked and prints the line: nothing else runs on the GPU or
+the host, and no timed step carries per-kernel events.  The initial weights are seeded (torch.manual_seed(rank)) and the batches are
+seeded, so the same arguments give the same inputs from run to run.
 
 Workload (BASELINE.json configs[1]): voice2pose_sdt_bp, 32 clips per GPU (weak scaling), 64-frame / 121-kpt clips
 (137 on-disk keypoints), fp32, synthetic seeded clips pre-staged in HBM.  One step = Voice2Pose.train_step without
@@ -14,6 +22,7 @@ Timing: W untimed warm-up steps, then exactly K steps between barrier + synchron
 slowest rank's wall time (the driver's contract).  Every step is also bracketed by one HIP event on the main stream, so the
 line carries the MEDIAN step time (SURVEY.md 8d's definition) and the mean over the steps that carried no per-kernel events.
 
+With --full:
 `roofline`        : the dominant kernel (the split-fp32 implicit-GEMM conv; with --no-f32-split the fp32-MFMA one): algorithmic FLOPs
                     per launch / mean launch duration from HIP events on the launching stream over sampled steps of the timed
                     region, against ITS matrix peak -- six bf16 MFMA products per fp32 product: the dense bf16 peak / 6 = 416.7
@@ -92,6 +101,30 @@ def stage_batches(n_batches, B, rank, dev):
                              "std": torch.from_numpy(rng.uniform(2.0, 30.0, (B, 242))).to(dev)},
         })
     return out
+
+
+DUMP_MAX_BYTES = 63 * 10 ** 6  # (64 MB in all with the .npy headers)
+
+
+def dump_outputs(directory, losses, results):
+    """--dump-outputs: what a caller of the timed step receives from its last call (forward_backward's losses and results dicts) as
+    DIR/losses.<name>.npy and DIR/results.<name>.npy; float64 stays float64, other floats become float32, integers and flags float64.
+    An array larger than its share of DUMP_MAX_BYTES is replaced by a fixed, seeded sample of its elements (flattened)."""
+    import numpy as np
+    arrays = {}
+    for group, d in (("losses", losses), ("results", results or {})):
+        for k, v in d.items():
+            if torch.is_tensor(v):  # (None entries, e.g. no condition code, are skipped)
+                v = v.detach()
+                v = v.double() if (v.dtype == torch.float64 or not v.is_floating_point()) else v.float()
+                arrays["%s.%s" % (group, k)] = v.cpu().numpy()
+    os.makedirs(directory, exist_ok=True)
+    share = DUMP_MAX_BYTES // max(1, len(arrays))
+    for name, a in sorted(arrays.items()):
+        if a.nbytes > share:
+            pick = np.random.Generator(np.random.PCG64(0)).choice(a.size, share // a.itemsize, replace=False)
+            a = a.reshape(-1)[np.sort(pick)]
+        np.save(os.path.join(directory, name + ".npy"), a)
 
 
 def cpu_baseline(B, steps=3):
@@ -225,9 +258,15 @@ def main(argv=None):
     ap.add_argument("--storage", default="f32", choices=["f32", "bf16"],
                     help="element type of the Conv2d chain's activations and conv operands in HBM: bf16 = BASELINE config 4's arithmetic "
                          "(bf16 tensors and MFMA products, fp32 accumulation / statistics / master weights); the metric is quoted on f32")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-alt-mode", action="store_true", help="skip the informational bf16-storage leg (BASELINE config 4's arithmetic) after the timed region")
-    ap.add_argument("--no-kernel-events", action="store_true", help="do not record per-launch HIP events (roofline leg)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need: per-kernel HIP events on sampled timed steps (roofline, roofline_conv1d), "
+                         "the informational legs behind the timed region (bf16 storage, pinned-host feed, graph replay) and the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the losses and results of the last timed step to DIR/<name>.npy (float32 / float64)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-alt-mode", action="store_true", help="with --full: skip the informational legs after the timed region (bf16 storage, "
+                                                               "BASELINE config 4's arithmetic; pinned-host feed; graph replay)")
+    ap.add_argument("--no-kernel-events", action="store_true", help="with --full: do not record per-launch HIP events (roofline leg)")
     ap.add_argument("--graph", action="store_true", help="replay the step from a captured hipGraph (N=1)")
     ap.add_argument("--graph-streams", action="store_true", help="with --graph: capture the side streams too (experiment)")
     ap.add_argument("--no-overlap-aux", action="store_true", help="keep the no-grad pose-encoder passes on the main stream")
@@ -239,7 +278,7 @@ def main(argv=None):
     ap.add_argument("--atomic-dw", action="store_true",
                     help="weight gradients with fp32 atomics (the round-2 default) instead of the ordered, bit-reproducible reductions")
     ap.add_argument("--bwd-wpc", default=None, help="experiment: persistent workgroups per CU of the backward stream-K plans, 'DX,DW' (e.g. 1,1 or 2,1)")
-    ap.add_argument("--dp-legs", action="store_true", help="N > 1: also run the informational legs behind the timed region (graph replay of the data-parallel step, bf16 storage) -- "
+    ap.add_argument("--dp-legs", action="store_true", help="with --full, N > 1: also run the informational legs behind the timed region (graph replay of the data-parallel step, bf16 storage) -- "
                                                            "they issue collectives on every rank; off by default between real ranks so that nothing behind the timed region can take the scaling number with it")
     ap.add_argument("--dp-graph-full", action="store_true", help="N > 1: the informational graph-replay legs capture the RCCL all-reduces WITH the step (graph.GraphedStep "
                     "mode 'full', the product default under SYS.HIP_GRAPH; exercised here on a 1-rank group only) instead of graph segments around an eager exchange ('split')")
@@ -257,9 +296,10 @@ def main(argv=None):
     stub = os.environ.get("SDT_BENCH_STUB") == "1"
     backend = os.environ.get("SDT_BENCH_BACKEND", "nccl")  # "nccl" is RCCL on ROCm; "gloo" only for the CPU control-flow test
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
-        # typed as a plain command: become the launcher (the reference spawns its own ranks too, main.py:60-69) -- re-exec under
-        # torch.distributed.run with one rank per GPU on this node; rank 0 of the children prints the JSON line
+        # typed as a plain command: become the launcher (the reference spawns its own ranks too, main.py:60-69) -- run
+        # torch.distributed.run with one rank per GPU on this node as a child process; rank 0 of the children prints the JSON line
         import socket
+        import subprocess
         with socket.socket() as sk:
             sk.bind(("127.0.0.1", 0))
             port = sk.getsockname()[1]
@@ -267,7 +307,7 @@ def main(argv=None):
         cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(args.gpus),
                "--master-addr", "127.0.0.1", "--master-port", str(port), os.path.abspath(__file__)] + list(sys.argv[1:] if argv is None else argv)
         sys.stdout.flush()
-        os.execv(sys.executable, cmd)
+        sys.exit(subprocess.call(cmd))
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
@@ -334,8 +374,9 @@ def main(argv=None):
         if args.dp_reserve is not None:
             from speechdrivestemplates_amd import dp as _dp
             _dp.RESERVED_SLOTS = args.dp_reserve
-        # every rank draws its own initial weights (nothing here seeds torch): setup_optimizer's dp.sync_replicas makes the
-        # replicas identical, as DDP's constructor does in the reference
+        # every rank draws its own initial weights, seeded so that the same arguments start from the same weights in every run (--dump-outputs):
+        # setup_optimizer's dp.sync_replicas makes the replicas identical, as DDP's constructor does in the reference
+        torch.manual_seed(rank)
         pipe, cfg = make_pipeline(args.config, N_CLIPS, batch_global=B * world,
                                   sys_opts={"STORAGE": args.storage, "CHAIN1D": not args.no_chain1d, "CONV_F32_SPLIT": not args.no_f32_split,
                                             "DISTRIBUTED": world > 1 or forced_dp})
@@ -344,20 +385,20 @@ def main(argv=None):
             pipe.reducer.launch_early = False
 
     def step(i):
-        losses, _ = pipe.forward_backward(batches[i % len(batches)])
+        losses, results = pipe.forward_backward(batches[i % len(batches)])
         pipe.optimizer_updates(losses)
-        return losses
+        return losses, results
 
     runner = step
     if args.graph and not stub:  # N > 1: the gradient exchange is part of the replayed step (graph.GraphedStep, "full" over RCCL)
         from speechdrivestemplates_amd.graph import GraphedStep
         gs = GraphedStep(pipe, warmup=min(3, max(1, args.warmup - 1)))
-        runner = lambda i: gs.run(batches[i % len(batches)])  # noqa: E731
+        runner = lambda i: (gs.run(batches[i % len(batches)]), gs.results)  # noqa: E731
 
     # (the event pools are created BEFORE the warm-up: creating and recording ~5000 events takes the host ~50 ms, the GPU idles and drops
     # its clocks meanwhile, and the first six timed steps then ran 0.2-2 ms slow -- 2.5 % of the driver's 20-step run)
     prof = prof_ovl = prof_dom = stages = None
-    if not stub and not args.no_kernel_events and not args.graph:
+    if args.full and not stub and not args.no_kernel_events and not args.graph:
         prof = ops.ConvProfiler(pool=2 * 200 * EVENT_STEPS_MAX)
         prof_dom = ops.ConvProfiler(pool=2 * 40 * EVENT_STEPS_MAX)  # short runs: "alone" steps that time the dominant kernel's launches only
         prof_ovl = ops.ConvProfiler(pool=2 * 200 * EVENT_STEPS_MAX) if ops.OVERLAP_DW else None
@@ -413,7 +454,7 @@ def main(argv=None):
                     ops.PROFILER, n_ovl = prof_ovl, n_ovl + 1
                 else:
                     ops.PROFILER, ops.OVERLAP_DW, n_alone = prof, False, n_alone + 1
-        losses = runner(args.warmup + i)
+        losses, results = runner(args.warmup + i)
     if marks is not None:
         marks[args.steps].record()
     else:
@@ -427,6 +468,8 @@ def main(argv=None):
         if on_gpu and not stub:  # a stream-K launch that gave up waiting for a partial tile would have left a code (and wrong results)
             codes = ops.streamk_error_codes()
             assert not codes, "stream-K error words: %r" % codes
+    if args.dump_outputs and rank == 0:  # before the --full legs below: they go on training the same pipeline
+        dump_outputs(args.dump_outputs, losses, results)
     prof_steps = n_alone
     if marks is not None:
         step_ms = [marks[i].elapsed_time(marks[i + 1]) for i in range(args.steps)]
@@ -627,10 +670,10 @@ def main(argv=None):
             return {"error": repr(e)[:300]}
 
     pcie = None
-    if not stub and on_gpu and world == 1 and not forced_dp and not args.graph and not args.no_alt_mode and args.storage == "f32" and args.conv_math == "f32":
+    if args.full and not stub and on_gpu and world == 1 and not forced_dp and not args.graph and not args.no_alt_mode and args.storage == "f32" and args.conv_math == "f32":
         pcie = pcie_leg()
     dp_graph = None
-    legs_ok = world == 1 or args.dp_legs  # (a forced 1-rank group keeps them: that is where they are tested)
+    legs_ok = args.full and (world == 1 or args.dp_legs)  # (a forced 1-rank group keeps them: that is where they are tested)
     if not stub and on_gpu and (world > 1 or forced_dp) and legs_ok and not args.graph and args.config == "voice2pose_sdt_bp" and not args.no_alt_mode:
         dp_graph = graph_leg_f32()  # every rank (collectives inside)
     alt = None
@@ -779,7 +822,7 @@ def main(argv=None):
             if "value" in alt:
                 alt["vs_default"] = alt["value"] / out["value_uninstrumented"]
             out["alt_conv_math"] = alt
-        if world == 1 and not args.no_cpu_baseline and not stub:
+        if args.full and world == 1 and not args.no_cpu_baseline and not stub:
             out["cpu_baseline"] = cpu_baseline(B)
             out["speedup_vs_cpu"] = out["value"] / out["cpu_baseline"]["value"]
         print(json.dumps(out), flush=True)

@@ -7,6 +7,8 @@ import os
 import subprocess
 import sys
 
+import pytest
+
 from conftest import REPO
 from test_dp_gloo import _free_port
 
@@ -53,3 +55,52 @@ def test_bench_single_rank_defaults():
     assert j["n_gpus"] == 1 and j["config"]["global_batch"] == 32 and j["vs_baseline"] is None
     for k in ("metric", "value", "unit", "ms_per_step", "higher_is_better", "dtype", "data", "median_ms_per_step"):
         assert k in j
+
+
+def test_bench_plain_run_is_lean_and_full_is_opt_in():
+    """A plain run times exactly --steps steps and carries none of the --full figures; --full is accepted (the stub has none to add)."""
+    j = _run(1, extra=("--steps", "7"))
+    assert j["steps"] == 7 and len(j["step_ms"]) == 7 and j["event_instrumented_steps"] == []
+    assert abs(j["ms_per_step"] - 32 * 1e3 / j["value"]) < 1e-6 * j["ms_per_step"]
+    for k in ("roofline", "roofline_conv1d", "cpu_baseline", "alt_conv_math", "pcie_inclusive", "dp_graph_replay"):
+        assert k not in j
+    j = _run(1, extra=("--full",))
+    assert j["steps"] == 5 and j["stub"] is True
+
+
+def test_bench_dump_outputs(tmp_path):
+    """--dump-outputs DIR: the losses of the last timed step as DIR/losses.<name>.npy (float32 / float64), written by rank 0 only."""
+    import numpy as np
+    for nproc in (1, 2):
+        d = tmp_path / ("r%d" % nproc)
+        _run(nproc, extra=("--dump-outputs", str(d)))
+        files = sorted(os.listdir(d))
+        assert files == ["losses.G_loss.npy"], files
+        a = np.load(d / files[0])
+        assert a.dtype in (np.float32, np.float64) and float(a) == 0.5
+
+
+@pytest.mark.gpu
+def test_bench_dump_outputs_on_the_gpu(tmp_path):
+    """A plain run of the real step: every array of the last timed step's losses and results is written, finite, float32 / float64, and a
+    second run with the same arguments starts from the same inputs and weights, so its losses agree (fp64-atomic statistics: 1e-6)."""
+    import numpy as np
+    dumps = []
+    for r in range(2):
+        d = tmp_path / ("run%d" % r)
+        out = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "2", "--dump-outputs", str(d)],
+                             capture_output=True, text=True, timeout=600, cwd=REPO)
+        assert out.returncode == 0, (out.stdout[-3000:], out.stderr[-3000:])
+        j = json.loads([ln for ln in out.stdout.splitlines() if ln.startswith("{")][-1])
+        assert j["steps"] == 3 and "roofline" not in j
+        dumps.append({f[:-4]: np.load(d / f) for f in os.listdir(d)})
+    a, b = dumps
+    for k in ("losses.G_loss", "losses.G_reg_loss", "losses.L2_dist", "results.poses_pred_batch", "results.mu_pred"):
+        assert k in a, sorted(a)
+    assert sorted(a) == sorted(b)
+    for k, v in a.items():
+        assert v.dtype in (np.float32, np.float64) and np.isfinite(v).all(), k
+    assert sum(v.nbytes for v in a.values()) <= 64e6
+    for k in a:
+        if k.startswith("losses."):
+            assert abs(float(a[k]) - float(b[k])) <= 1e-6 * abs(float(b[k])) + 1e-7, (k, float(a[k]), float(b[k]))

@@ -64,25 +64,18 @@ def test_lr_schedule_resume_needs_initial_lr():
 def test_frame_variant_codes_are_rejected_like_the_reference_rejects_them():
     """VOICE2POSE.GENERATOR.CLIP_CODE.FRAME_VARIANT (voice2pose.py:66-67,148-150): the reference's own generator cannot take the (B,D,T) code
     that branch produces -- generator.py:110 calls repeat([1,1,T]) on a 4-D tensor -- so the key is dead in the reference; this build raises at
-    construction.  Where the reference sources are present (the authoring container) the reference's failure is re-probed."""
+    construction.  The reference's failure is recorded in tests/golden/reference_probes.json."""
     import os
-    import sys
     from speechdrivestemplates_amd.config import get_cfg_defaults
     cfg = get_cfg_defaults()
     assert cfg.VOICE2POSE.GENERATOR.CLIP_CODE.FRAME_VARIANT is False  # the default, and no shipped yaml changes it
     src = open(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "speechdrivestemplates_amd", "core", "pipelines",
                             "voice2pose.py")).read()
     assert "if code.FRAME_VARIANT:" in src and "raise RuntimeError('VOICE2POSE.GENERATOR.CLIP_CODE.FRAME_VARIANT" in src
-    if os.path.isdir("/root/reference/core/networks"):
-        import subprocess
-        code = ("import torch\nfrom types import SimpleNamespace as NS\nfrom core.networks import get_model\n"
-                "cfg = NS(VOICE2POSE=NS(GENERATOR=NS(LEAKY_RELU=True, NORM='IN', CLIP_CODE=NS(DIMENSION=32))), DATASET=NS(NUM_LANDMARKS=121))\n"
-                "G = get_model('SequenceGeneratorCNN')(cfg)\n"
-                "try:\n    G(torch.randn(1, 80, 427), 64, torch.randn(1, 32, 64))\n    print('ACCEPTED')\n"
-                "except RuntimeError as e:\n    print('RAISES', e)\n")
-        out = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, timeout=300, cwd="/tmp",
-                             env=dict(os.environ, PYTHONPATH="/root/reference", PYTHONDONTWRITEBYTECODE="1"))
-        assert "RAISES" in out.stdout and "repeat dims" in out.stdout, (out.stdout, out.stderr[-500:])
+    import json
+    probes = json.load(open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "reference_probes.json")))
+    out = probes["frame_variant_code"]  # the reference generator fed that code (tests/golden/make_reference_probes.py)
+    assert "RAISES" in out and "repeat dims" in out, out
 
 
 def test_chain_wiring_of_the_generator():

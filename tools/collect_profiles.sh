@@ -7,8 +7,8 @@ cd "$GRAFT_REPO_ROOT"
 OUT=gpurun_out/${TAG}_final
 rm -rf "$OUT"; mkdir -p "$OUT"
 CMD="python bench.py --steps 30 --warmup 5 --no-cpu-baseline --no-alt-mode"
-# (1) the bench line as the driver runs it
-python bench.py > "$OUT/bench.json" 2> "$OUT/bench.err"
+# (1) the bench line with its --full figures (the roofline read below)
+python bench.py --full > "$OUT/bench.json" 2> "$OUT/bench.err"
 # (2) kernel trace + stats of the same command (default: weight gradients on the side stream)
 timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/trace" -o b -- $CMD > "$OUT/trace.log" 2>&1
 # (3) every kernel alone on the GPU

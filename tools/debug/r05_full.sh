@@ -4,8 +4,8 @@ timeout 3000 python -m pytest tests -m gpu -q ${PYTEST_ARGS:--x} > gpurun_out/r5
 echo "pytest rc $?" >> gpurun_out/r5_full_pytest.txt
 tail -15 gpurun_out/r5_full_pytest.txt
 if [ "$NOBENCH" = "" ]; then
-timeout 600 python bench.py --steps 20 --warmup 5 > gpurun_out/r5_full_bench.txt 2>&1
-tail -1 gpurun_out/r5_full_bench.txt | python -c "
+BENCH_LINE=$(timeout 600 python bench.py --full --steps 20 --warmup 5 | tail -1)
+echo "$BENCH_LINE" | python -c "
 import sys,json
 d=json.loads(sys.stdin.read())
 print('fp32', round(d['value'],1), 'clips/s', round(d['ms_per_step'],3), 'ms; roofline', round(d['roofline']['frac'],4))
