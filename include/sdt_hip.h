@@ -429,6 +429,35 @@ int sdt_clip_poses_prepare_f32(const float* raw, const int64_t* idx, const float
                                float* score, int N, int Tstore, int B, int T, int hierarchical, void* stream);
 int sdt_rows_gather_f32(const float* src, const int64_t* idx, float* dst, int N, int B, int64_t n_cols, void* stream);
 
+/*
+ * Skeleton rendering (core/utils/keypoint_visualization.py:8-110,177-207: draw_body_parts, vis_relative_pose_clip,
+ * vis_relative_pose_pair_clip, draw_pose_frames_in_long_img; DESIGN.md section 10 is the drawing contract).
+ * A launch draws n_images images of H x W BGR uint8 pixels, (n_images, H, W, 3) row-major.  Each image is the list of
+ * its n_inst instances (instance k of image i = inst[i*n_inst + k]), drawn in that order; an instance is one pose of
+ * the skeleton table of K in {121, 135, 137} keypoints (sdt_render_edges(K) = 108 / 109 / 109 edges).
+ * Endpoint of keypoint j: (int)(p[j]*scale + off) with the multiply and the add rounded separately (float64, no FMA),
+ * truncated toward zero, then shifted by shift_x columns.  An edge with a non-finite endpoint or |p*scale + off| > 2^24,
+ * or of an instance whose pose index lies outside [0, n_poses), is not drawn and is counted in *skipped (nullable).
+ * Workspace: sdt_render_workspace_bytes(n_images, n_inst, K) bytes; prepare writes all of it (one record of 16 int32 per
+ * stroke: x0 y0 x1 y1 | bbox x0 y0 x1 y1, inclusive, empty if x0 > x1 | the segment clipped near the window, 4 floats |
+ * B | G<<8 | R<<16 | thickness<<24, clip_x0, clip_x1, drawn), skeleton_u8 reads it and writes every output byte.
+ */
+typedef struct sdt_render_instance {
+    int64_t pose;             /* index of the (2, K) float64 pose slice: x row then y row */
+    double off_x, off_y;      /* canvas centre, added after the multiply */
+    double scale;             /* VISUALIZATION_SCALING (1.0 for the long image) */
+    int32_t shift_x;          /* integer column origin of the instance's window (long image), added after truncation */
+    int32_t clip_x0, clip_x1; /* columns [clip_x0, clip_x1) the instance may touch (clamped to [0, W)) */
+    int32_t reserved;
+} sdt_render_instance;
+
+int64_t sdt_render_workspace_bytes(int n_images, int n_inst, int K);
+int sdt_render_edges(int K);
+int sdt_render_prepare_f64(const double* poses, int64_t n_poses, int K, const sdt_render_instance* inst, int n_images, int n_inst,
+                           int H, int W, void* workspace, int64_t workspace_bytes, int32_t* skipped, void* stream);
+int sdt_render_skeleton_u8(const void* workspace, int64_t workspace_bytes, int n_images, int n_inst, int K, int H, int W,
+                           uint8_t* out, int64_t out_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

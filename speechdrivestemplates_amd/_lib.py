@@ -118,6 +118,10 @@ SIGNATURES = {
     "sdt_convsk_set_spin_limit": [C.c_uint],
     "sdt_convsk_set_k_order": [_i],
     "sdt_convsk_set_dw_wide_tiles": [_i],
+    "sdt_render_workspace_bytes": [_i, _i, _i],  # (returns int64_t: restype set in load())
+    "sdt_render_edges": [_i],
+    "sdt_render_prepare_f64": [_p, _i64, _i, _p, _i, _i, _i, _i, _p, _i64, _p, _p],
+    "sdt_render_skeleton_u8": [_p, _i64, _i, _i, _i, _i, _i, _p, _i64, _p],
 }
 F32, BF16 = 0, 1  # enum sdt_dtype
 
@@ -159,6 +163,7 @@ def load():
         fn = getattr(lib, name)  # AttributeError if the symbol is missing
         fn.argtypes = argtypes
         fn.restype = C.c_int
+    lib.sdt_render_workspace_bytes.restype = C.c_int64
     lib.sdt_conv_dw_group_plan_bytes.argtypes = [_i]
     lib.sdt_conv_dw_group_plan_bytes.restype = C.c_int64
     lib.sdt_conv_dw_workspace_bytes.argtypes = [_G]

@@ -46,6 +46,9 @@ _DEFAULTS = {
             # that two training processes share must not run two of them at once (each would wait for CUs the other one holds until the spin limit
             # trips and the Trainer raises)
             "STORAGE": "f32", "HIP_GRAPH": False, "CHAIN1D": True,
+            # RENDER_VIDEO True = TRAIN/TEST.SAVE_VIDEO and the demo write the reference's videos and long images, drawn on the GPU
+            # (render.py, video.py; mp4 needs an ffmpeg executable, else the JPEG frames + wav are kept).  False = npz output only.
+            "RENDER_VIDEO": False,
             # CONV_F32_SPLIT (fp32 tensors): Conv2d products as six bf16 MFMA products of an exact three-way bf16 split of both operands, fp32
             # accumulation (csrc/convbf.hip; fp32-grade results, 1.3x faster); False = the fp32-MFMA kernels of rounds 3-4
             "CONV_F32_SPLIT": True,

@@ -98,17 +98,26 @@ class Pose2Pose(Trainer):
     def train_step(self, batch, t_step, global_step, epoch):
         # SYS.HIP_GRAPH: ~150 launches of a few microseconds -- enqueued one by one the step is bound by the host (3 ms); replayed from a hipGraph
         # (one GPU or data-parallel: graph.GraphedStep) it is not
-        losses, _ = self.graphed_or_eager_step(batch)
+        # SYS.RENDER_VIDEO + TRAIN.SAVE_VIDEO: save steps run eagerly and draw clip 0 (pose2pose.py:156-169); never inside a capture
+        video_step = (self.rendering() and self.cfg.TRAIN.SAVE_VIDEO and self.is_master_process() and self.base_path is not None
+                      and t_step % self.result_saving_interval_train == 0)
+        losses, results = self.graphed_or_eager_step(batch, eager_ok=not video_step)
         self.last_losses = losses
         if t_step % self.cfg.SYS.LOG_INTERVAL == 0:
             if self.cfg.SYS.DISTRIBUTED:
                 self.check_kernels_all_ranks(dp.reduce_scalars(losses, error_flag=ops.kernel_error_flag()))
             if self.is_master_process():
                 self.logger_writer_step('TRAIN', losses, t_step, epoch, global_step)
+        if video_step:
+            dev = self.model.clip_code_mu.device
+            stat = batch['speaker_stat']
+            fin_p, fin_g, _ = ops.final_metrics(results['poses_pred_batch'].detach(), results['poses_gt_batch'], stat['mean'].to(dev),
+                                                stat['std'].to(dev), stat['scale_factor'].to(dev), bool(self.cfg.DATASET.HIERARCHICAL_POSE), True)
+            self.write_pair_video('TRAIN', fin_p[0], fin_g[0], t_step, epoch, global_step, batch.get('audio'))
 
     @torch.no_grad()
     def test_step(self, batch, t_step, epoch=0):
-        """Validation / test step of the pose VAE (pose2pose.py:172-217) without the video writer."""
+        """Validation / test step of the pose VAE (pose2pose.py:172-217); videos only with SYS.RENDER_VIDEO."""
         tag = 'TEST' if epoch == 0 else 'VAL'
         dev = self.model.clip_code_mu.device
         self.apply_knobs()
@@ -134,16 +143,20 @@ class Pose2Pose(Trainer):
             if t_step % self.result_saving_interval_test == 0 and self.cfg.TEST.SAVE_NPZ and self.base_path is not None:
                 self.save_results(tag, t_step, epoch, self.base_path,
                                   {k: v.detach().cpu().numpy() for k, v in results.items() if torch.is_tensor(v)})
+            if t_step % self.result_saving_interval_test == 0 and self.cfg.TEST.SAVE_VIDEO and self.rendering() and self.base_path is not None:
+                self.write_pair_video(tag, fin_p[0], fin_g[0], t_step, epoch, audio=batch.get('audio'))  # pose2pose.py:208-214
         return {k: v.detach() * self.cfg.TEST.BATCH_SIZE for k, v in losses.items()}, {}
 
 
     @torch.no_grad()
     def demo_step(self, batch, t_step=0, epoch=0, extra_id=None, interpolation_coeff=None):
-        """Decode a stored clip code into a pose sequence (pose2pose.py:219-244) without the video writer."""
+        """Decode a stored clip code into a pose sequence (pose2pose.py:219-244); video + long image with SYS.RENDER_VIDEO."""
         self.model.eval()
         results = self.model(batch, return_loss=False, interpolation_coeff=interpolation_coeff)
         results['poses_pred_batch'] = self.test_dataset.get_final_results(results['poses_pred_batch'].detach(), batch['speaker_stat'])
         if self.is_master_process() and self.cfg.TEST.SAVE_NPZ and self.base_path is not None:
             self.save_results('DEMO', t_step, epoch, self.base_path,
                               {k: v.detach().cpu().numpy() for k, v in results.items() if torch.is_tensor(v)}, extra_id=extra_id)
+        if self.is_master_process() and self.cfg.TEST.SAVE_VIDEO and self.rendering() and self.base_path is not None:
+            self.write_demo_video(results['poses_pred_batch'][0], t_step, epoch, batch.get('audio'), extra_id)
         return results

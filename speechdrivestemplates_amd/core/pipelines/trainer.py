@@ -1,7 +1,8 @@
 """Training-loop shell around ``train_step`` (core/pipelines/trainer.py): rank helpers (:29-45), dataset /
 dataloader setup (:64-145), experiment setup with resume / pretrain (:162-224), step logging (:242-263),
-checkpoint wire format (:305-321), epoch loop (:367-405) and validation (:407-427).  TensorBoard / video
-output of the reference are out of scope; scalars go to the Python logger."""
+checkpoint wire format (:305-321), epoch loop (:367-405) and validation (:407-427).  TensorBoard output of the
+reference is out of scope; scalars go to the Python logger.  Pose videos and long images are drawn on
+the GPU (render.py) and written by video.VideoWriter when SYS.RENDER_VIDEO is set (opt-in; default: npz only)."""
 import logging
 import os
 import time
@@ -171,10 +172,48 @@ class Trainer(object):
                                "last check are invalid on every rank (see that rank's message)" % int(flagged))
 
     def close(self):
-        """Give back what this pipeline holds process-wide (the data-parallel reducer's workgroup-slot reserve, dp.GradReducer.close)."""
+        """Give back what this pipeline holds process-wide (the data-parallel reducer's workgroup-slot reserve, dp.GradReducer.close)
+        and drain the asynchronous video writer."""
         r = getattr(self, 'reducer', None)
         if r is not None:
             r.close()
+        vw = getattr(self, 'video_writer', None)
+        if vw is not None:
+            vw.close()
+            self.video_writer = None
+
+    # -- videos (trainer.py:374,437,467; voice2pose.py:318-331,372-378,404-410,448-459) -----------------------------------
+    def rendering(self):
+        """SYS.RENDER_VIDEO: TRAIN/TEST.SAVE_VIDEO and the demo write videos / long images (drawn on the GPU)"""
+        return bool(getattr(self.cfg.SYS, 'RENDER_VIDEO', False))
+
+    def setup_video_writer(self):
+        if self.rendering() and self.is_master_process() and getattr(self, 'video_writer', None) is None:
+            from ...video import VideoWriter
+            self.video_writer = VideoWriter(self.cfg)
+        return getattr(self, 'video_writer', None)
+
+    def generate_video_pair(self, relative_poses_pred, relative_poses_gt):
+        from ... import render
+        return render.render_pose_pair_clip(relative_poses_pred, relative_poses_gt, tuple(self.cfg.SYS.CANVAS_SIZE),
+                                            self.cfg.SYS.VISUALIZATION_SCALING)
+
+    def generate_video(self, relative_poses):
+        from ... import render
+        return render.render_pose_clip(relative_poses, tuple(self.cfg.SYS.CANVAS_SIZE), self.cfg.SYS.VISUALIZATION_SCALING)
+
+    def write_pair_video(self, tag, pred, gt, t_step, epoch, global_step=None, audio=None):
+        """clip 0's prediction beside its ground truth, with clip 0's audio (final poses, (T, 2, K))"""
+        vid_batch = self.generate_video_pair(pred, gt)
+        self.setup_video_writer().save_video(self.cfg, tag, vid_batch, t_step, epoch, global_step,
+                                             audio=None if audio is None else audio[0], base_path=self.base_path)
+
+    def write_demo_video(self, pred, t_step, epoch, audio=None, extra_id=None):
+        from ... import render
+        vid_batch = self.generate_video(pred)
+        long_img = render.render_long_image(pred)
+        self.setup_video_writer().save_video(self.cfg, 'DEMO', vid_batch, t_step, epoch, long_img=long_img,
+                                             audio=None if audio is None else audio[0], base_path=self.base_path, extra_id=extra_id)
 
     def _set_reducer(self, reducer):
         self.close()  # a second setup_optimizer on this pipeline: the old reducer's reserve goes back first
@@ -243,6 +282,7 @@ class Trainer(object):
         """``pipeline.train(cfg, exp_tag, args.resume_from)`` as main.py:51 calls it (trainer.py:367).  ``cfg`` is the object
         the pipeline was constructed with; like the reference, the loop reads ``self.cfg``."""
         self.base_path, epoch_start, global_step = self.setup_experiment(True, exp_tag, resume_from=resume_from)
+        self.setup_video_writer()  # (trainer.py:374; only with SYS.RENDER_VIDEO, on the master process)
         if self.cfg.SYS.DISTRIBUTED:
             torch.distributed.barrier()
         for epoch in range(epoch_start, self.cfg.TRAIN.NUM_EPOCHS):
@@ -295,6 +335,7 @@ class Trainer(object):
     def test(self, cfg, exp_tag, checkpoint):
         """``pipeline.test(cfg, exp_tag, args.checkpoint)`` (main.py:48, trainer.py:429)."""
         self.base_path = self.setup_experiment(False, exp_tag, checkpoint=checkpoint)
+        self.setup_video_writer()
         return self.validate(self.test_dataloader, 0)
 
     @torch.no_grad()
@@ -303,6 +344,7 @@ class Trainer(object):
         code interpolation coefficient swept over [0, 1].  Returns the list of results dicts (the reference only writes
         videos / npz files)."""
         self.base_path = self.setup_experiment(False, exp_tag, checkpoint=checkpoint, demo_input=demo_input)
+        self.setup_video_writer()
         self.model.eval()
         out = []
         for t_step, batch in enumerate(self.test_dataloader):

@@ -325,10 +325,14 @@ class Voice2Pose(Trainer):
         if save_step and self.is_master_process() and self.cfg.TRAIN.SAVE_NPZ:
             self.save_results(tag, t_step, epoch, self.base_path,
                               {k: v.detach().cpu().numpy() for k, v in results.items() if torch.is_tensor(v)})
+        if save_step and self.is_master_process() and self.cfg.TRAIN.SAVE_VIDEO and self.rendering() and self.base_path is not None:
+            # voice2pose.py:325-331: clip 0, prediction beside ground truth, with its audio (save steps run eagerly: final poses)
+            self.write_pair_video(tag, results['poses_pred_batch'][0], results['poses_gt_batch'][0], t_step, epoch, global_step,
+                                  batch['audio'])
 
     @torch.no_grad()
     def test_step(self, batch, t_step, epoch=0):
-        """Validation / test step (voice2pose.py:333-384) without the video writer."""
+        """Validation / test step (voice2pose.py:333-384); videos only with SYS.RENDER_VIDEO."""
         tag = 'TEST' if epoch == 0 else 'VAL'
         dev = self.model._device()
         self.apply_knobs()
@@ -351,13 +355,15 @@ class Voice2Pose(Trainer):
             if t_step % self.result_saving_interval_test == 0 and self.cfg.TEST.SAVE_NPZ and self.base_path is not None:
                 self.save_results(tag, t_step, epoch, self.base_path,
                                   {k: v.detach().cpu().numpy() for k, v in results.items() if torch.is_tensor(v)})
+            if t_step % self.result_saving_interval_test == 0 and self.cfg.TEST.SAVE_VIDEO and self.rendering() and self.base_path is not None:
+                self.write_pair_video(tag, fin_p[0], fin_g[0], t_step, epoch, audio=batch['audio'])  # voice2pose.py:372-378
         batch_losses = {k: v.detach() * self.cfg.TEST.BATCH_SIZE for k, v in losses.items()}
         keep = ('mu_pred', 'mu_gt', 'logvar_pred', 'logvar_gt', 'condition_code')
         return batch_losses, {k: v.detach().cpu().numpy() for k, v in results.items() if k in keep and v is not None}
 
     @torch.no_grad()
     def demo_step(self, batch, t_step=0, epoch=0, extra_id=None, interpolation_coeff=None):
-        """Variable-length inference from raw audio (voice2pose.py:386-410 without the video writer): batch['audio'] is
+        """Variable-length inference from raw audio (voice2pose.py:386-410; video + long image with SYS.RENDER_VIDEO): batch['audio'] is
         (1, L) with L cropped to a whole number of 1/15 s frames, batch['num_frames'] = L // (16000/15) (up to 360 for the
         reference's 24 s demo limit); returns de-normalised global poses (1, T, 2, 121) in float64."""
         self.model.eval()
@@ -367,6 +373,8 @@ class Voice2Pose(Trainer):
         if self.is_master_process() and self.cfg.TEST.SAVE_NPZ and self.base_path is not None:
             self.save_results('DEMO', t_step, epoch, self.base_path,
                               {k: v.detach().cpu().numpy() for k, v in results.items() if torch.is_tensor(v)}, extra_id=extra_id)
+        if self.is_master_process() and self.cfg.TEST.SAVE_VIDEO and self.rendering() and self.base_path is not None:
+            self.write_demo_video(results['poses_pred_batch'][0], t_step, epoch, batch['audio'], extra_id)
         return results
 
     def evaluate_step(self, results_dict):
