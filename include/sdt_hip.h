@@ -458,6 +458,32 @@ int sdt_render_prepare_f64(const double* poses, int64_t n_poses, int K, const sd
 int sdt_render_skeleton_u8(const void* workspace, int64_t workspace_bytes, int n_images, int n_inst, int K, int H, int W,
                            uint8_t* out, int64_t out_bytes, void* stream);
 
+/*
+ * A speaker's pose statistics (data_preprocess/4_1_calculate_mean_std.py:59-116,193-225 and 4_2_parse_mean_std_npz.py:16-23;
+ * DESIGN.md section 11 is the contract).  The training clips are split into num_chunks chunks of rows_per_chunk clips; clip j of
+ * chunk c is (num_frames, 2, 137) x / y in pixels, float32 (elem_bytes 4) or float64 (elem_bytes 8), at
+ * poses + c*chunk_pitch + (j - first_row)*num_frames*274 elements for j in [first_row, first_row + window).
+ * accumulate advances, for every (chunk, frame, keypoint) and both modes (parted = pose_np_deduct_root, global = root only), the
+ * running mean (pass 1, cal_mean_*: avg = avg*w + (1-w)*q, w = n/(n+1)) or the running variance around the pass-1 means
+ * (pass 2, cal_std_*: var = var*w + (1-w)*(q - M)**2; mean137 = finalize's out137 of pass 1) over the window's clips in order,
+ * skipping a keypoint when |q_x + root_x| < 5 and |q_y + root_y| < 5.  The root deduction and that test are computed in the
+ * pose element type, the rest in float64 with every operation rounded on its own.  first_row == 0 starts from zero; later
+ * windows continue from the state buffer (sdt_speaker_stats_state_bytes(num_chunks, num_frames) bytes, float64).  A non-finite
+ * x / y is recorded as the first such row (c*rows_per_chunk + j) of its lane.
+ * finalize (one launch per pass): out137 (2 modes parted / global, 2 coordinates, 137) = the per-chunk tables averaged over
+ * chunks, then frames, in index order (pass 2: the square root of each chunk's variance first, :116); out242 (2 modes, 242) =
+ * the same without 4_2's 16 deleted keypoints, x row then y row; counts (2, 137) = kept detections; first_bad_row (137) = 1 + the
+ * first row with a non-finite coordinate of that keypoint, 0 if none; flags (2, 137): bit 0 = a non-finite result,
+ * bit 1 (pass 2) = a kept keypoint with a zero std.  No allocation; every pointer is a device buffer; every index is checked
+ * against the sizes given.
+ */
+int64_t sdt_speaker_stats_state_bytes(int num_chunks, int num_frames);
+int sdt_speaker_stats_accumulate(int pass, int elem_bytes, const void* poses, int64_t poses_elems, int64_t chunk_pitch, int num_chunks,
+                                 int num_frames, int window, int64_t first_row, int64_t rows_per_chunk, const double* mean137, void* state,
+                                 int64_t state_bytes, void* stream);
+int sdt_speaker_stats_finalize(int pass, const void* state, int64_t state_bytes, int num_chunks, int num_frames, double* out137,
+                               double* out242, double* counts, int64_t* first_bad_row, int32_t* flags, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

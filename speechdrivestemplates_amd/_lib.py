@@ -122,6 +122,9 @@ SIGNATURES = {
     "sdt_render_edges": [_i],
     "sdt_render_prepare_f64": [_p, _i64, _i, _p, _i, _i, _i, _i, _p, _i64, _p, _p],
     "sdt_render_skeleton_u8": [_p, _i64, _i, _i, _i, _i, _i, _p, _i64, _p],
+    "sdt_speaker_stats_state_bytes": [_i, _i],  # (returns int64_t: restype set in load())
+    "sdt_speaker_stats_accumulate": [_i, _i, _p, _i64, _i64, _i, _i, _i, _i64, _i64, _p, _p, _i64, _p],
+    "sdt_speaker_stats_finalize": [_i, _p, _i64, _i, _i, _p, _p, _p, _p, _p, _p],
 }
 F32, BF16 = 0, 1  # enum sdt_dtype
 
@@ -164,6 +167,7 @@ def load():
         fn.argtypes = argtypes
         fn.restype = C.c_int
     lib.sdt_render_workspace_bytes.restype = C.c_int64
+    lib.sdt_speaker_stats_state_bytes.restype = C.c_int64
     lib.sdt_conv_dw_group_plan_bytes.argtypes = [_i]
     lib.sdt_conv_dw_group_plan_bytes.restype = C.c_int64
     lib.sdt_conv_dw_workspace_bytes.argtypes = [_G]

@@ -30,6 +30,9 @@ _DEFAULTS = {
         "AUDIO_SR": 16000, "FPS": 15, "CACHING": False,
         # extension (not in the reference): number of clips of the seeded synthetic dataset used by bench/tests
         "SYNTHETIC_CLIPS": 4096,
+        # extension: an npz of DATASET.SPEAKER's statistics (python -m speechdrivestemplates_amd.speaker_stats),
+        # registered on every rank before any dataset is built -- the reference's "paste into speakers_stat.py" step.  None: built-in only
+        "SPEAKER_STAT_FILE": None,
     },
     "TRAIN": {"NUM_EPOCHS": 100, "BATCH_SIZE": 32, "SAVE_VIDEO": True, "SAVE_NPZ": False, "LR": 1e-4, "WD": 0,
               "LR_SCHEDULER": True, "PRETRAIN_FROM": None, "VALIDATE": True, "NUM_RESULT_SAMPLE": 2,

@@ -40,7 +40,10 @@ class PoseTransforms:
     # per step.  The device tensor of an entry is NEVER freed or replaced (a captured hipGraph reads it by raw pointer: the caching allocator
     # would hand the memory to somebody else and every replay would normalise with garbage, silently -- ADVICE r5); an array whose bytes changed
     # (in-place edit of a registered mean / std: a 2 KB compare per call) is copied INTO the same tensor, which also makes the edit visible to
-    # replays.  The table only grows; past _STAT_CACHE_MAX distinct arrays further ones are uploaded per call (correct, slower, not capturable).
+    # replays.  A tensor is reachable from ONE key at a time: when a re-registration hands it to the new array, the old array's key is dropped
+    # (the new entry keeps the tensor alive), so a later call with the old array uploads its own copy instead of writing into the new
+    # statistics.  The table only grows; past _STAT_CACHE_MAX distinct arrays further ones are uploaded per call (correct,
+    # slower, not capturable).
     _STAT_ON_DEVICE = {}
     _STAT_CACHE_MAX = 256
 
@@ -63,7 +66,7 @@ class PoseTransforms:
                 PoseTransforms._no_capture("were replaced")
                 ent[1].copy_(torch.tensor(n.astype(np.float64), dtype=torch.float32).reshape(ent[1].shape))
                 PoseTransforms._STAT_ON_DEVICE[(id(n), key[1])] = [n, ent[1], n.tobytes()]
-                ent[2] = None  # the old array no longer describes the tensor: a later call with it re-uploads (into the same tensor again)
+                del PoseTransforms._STAT_ON_DEVICE[key]  # the tensor now belongs to n alone: a later call with o gets a tensor of its own
 
     def _stat(self, t, kp):
         K = self.cfg.NUM_LANDMARKS
@@ -71,7 +74,7 @@ class PoseTransforms:
             key = (id(t), str(kp.device))
             hit = PoseTransforms._STAT_ON_DEVICE.get(key)
             raw = t.tobytes()
-            if hit is not None and hit[0] is t and hit[2] != raw:  # edited in place (or re-homed away): refresh the SAME device tensor
+            if hit is not None and hit[0] is t and hit[2] != raw:  # edited in place: refresh the SAME device tensor
                 self._no_capture("changed")
                 hit[1].copy_(torch.tensor(t.astype(np.float64), dtype=torch.float32).reshape(hit[1].shape))
                 hit[2] = raw
@@ -342,6 +345,19 @@ def load_builtin_speaker_stats():
         if name not in dst:
             pre = '%s/%s/' % (table, name)
             dst[name] = {'scale_factor': float(data[pre + 'scale_factor']), 'mean': data[pre + 'mean'], 'std': data[pre + 'std']}
+
+
+def register_configured_speaker_stats(cfg):
+    """DATASET.SPEAKER_STAT_FILE (an npz written by speaker_stats.save_speaker_stats) -> the statistics of DATASET.SPEAKER; None: nothing"""
+    path = cfg.DATASET.SPEAKER_STAT_FILE
+    if path is None:
+        return False
+    if cfg.DATASET.SPEAKER is None:
+        raise ValueError('DATASET.SPEAKER_STAT_FILE is set but DATASET.SPEAKER is not: whose statistics are they?')
+    if not os.path.exists(path):
+        raise FileNotFoundError('DATASET.SPEAKER_STAT_FILE: no such file: %s' % path)
+    load_speaker_stats(path, cfg.DATASET.SPEAKER)
+    return True
 
 
 def load_speaker_stats(npz_path, name):

@@ -13,6 +13,7 @@ import torch
 from torch.utils.data import DataLoader
 
 from ..datasets import get_dataset
+from ..datasets.gesture_dataset import register_configured_speaker_stats
 
 
 def _collate_stat(samples):
@@ -52,6 +53,7 @@ class Trainer(object):
     # -- data ------------------------------------------------------------------------------------------
     def setup_dataset(self, cfg, split, demo_input=None):
         ws = self.get_world_size()
+        register_configured_speaker_stats(cfg)  # DATASET.SPEAKER_STAT_FILE, before any dataset looks its speaker up
         ds_cls = get_dataset(cfg.DATASET.NAME)
         if split == 'train':
             self.train_dataset = ds_cls(cfg.DATASET.ROOT_DIR if cfg.DATASET.NAME == 'GestureDataset' else None,
