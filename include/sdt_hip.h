@@ -484,6 +484,40 @@ int sdt_speaker_stats_accumulate(int pass, int elem_bytes, const void* poses, in
 int sdt_speaker_stats_finalize(int pass, const void* state, int64_t state_bytes, int num_chunks, int num_frames, double* out137,
                                double* out242, double* counts, int64_t* first_bad_row, int32_t* flags, void* stream);
 
+/*
+ * The per-epoch clip-code figure (core/pipelines/voice2pose.py:479-510 and pose2pose.py:314-345, draw_figure_epoch: PCA(n_components=2)
+ * of the clip-code table and plt.scatter of the projection; logged by core/pipelines/trainer.py:404-405,281-283; DESIGN.md section 12
+ * is the contract).  x is the (n_rows, dim) fp32 table, 2 <= dim <= 64, 2 <= n_rows <= 2^30; all arithmetic is float64.
+ * Workspace: sdt_code_pca_workspace_bytes(n_rows, dim) bytes (0: unsupported sizes), shared by moments and project, never read before
+ * it is written.  No allocation; every pointer is a device buffer; every index is checked against the sizes given.
+ *   moments (voice2pose.py:495-498, the centring and the scatter matrix inside pca.fit): mean (dim) = column sums / n_rows,
+ *     cov (dim, dim) = centred products / (n_rows - 1), both from per-workgroup partials reduced in workgroup order (fixed grid, no
+ *     floating-point atomics: the same bits on every call).  first_bad_row[0] = 1 + the first row with a non-finite entry, 0 if none.
+ *   eigh (the decomposition inside pca.fit): cyclic Jacobi, one workgroup, until off(A) <= rel_tol * ||cov||_F.  evals (dim),
+ *     descending; comps (2, dim) = the two leading eigenvectors, each signed so that its entry of largest magnitude (first of equals)
+ *     is positive; info (4) = sweeps done, final off-diagonal Frobenius norm, ||cov||_F, trace(cov); err[0]: bit 0 = not converged
+ *     within max_sweeps, bit 1 = trace(cov) is not positive.
+ *   project (voice2pose.py:499, pca.transform): X (n_rows, 2) float64 = (x - mean) . comps^T, dim ascending; limits (8) = min0, max0,
+ *     min1, max1 of X, then the axis limits lo0, hi0, lo1, hi1 = min - 0.05 span, max + 0.05 span (an axis with hi <= lo:
+ *     [min - 0.5, max + 0.5]).
+ *   raster (voice2pose.py:500, plt.scatter(alpha=0.2, edgecolors='none', s=1)): plot rectangle = the canvas inset by `margin` pixels
+ *     with a 1-pixel black ring around it.  Point n -> column min(int(floor((X0 - lo0) * (Pw / (hi0 - lo0)))), Pw - 1), row likewise on
+ *     axis 1 and flipped, every operation rounded on its own; the marker_px x marker_px block from (col - (marker_px-1)/2,
+ *     row - (marker_px-1)/2), clipped to the rectangle, is counted into counts (Ph, Pw) uint32 with integer atomics; points outside
+ *     axis_limits (4: lo0, hi0, lo1, hi1) or not finite are skipped.  Then out (H, W, 3) uint8 RGB = table[min(count, table_len - 1)]
+ *     inside the rectangle (table: (table_len, 3) uint8, entry k = k markers composited over white), white outside.  The CALLER zeroes
+ *     counts before the call; the kernels leave the counts in it.
+ */
+int64_t sdt_code_pca_workspace_bytes(int64_t n_rows, int dim);
+int sdt_code_pca_moments(const float* x, int64_t n_rows, int dim, void* workspace, int64_t workspace_bytes, double* mean, double* cov,
+                         int64_t* first_bad_row, void* stream);
+int sdt_code_pca_eigh(const double* cov, int dim, int max_sweeps, double rel_tol, double* evals, double* comps, double* info, int32_t* err,
+                      void* stream);
+int sdt_code_pca_project(const float* x, int64_t n_rows, int dim, const double* mean, const double* comps, double* X, void* workspace,
+                         int64_t workspace_bytes, double* limits, void* stream);
+int sdt_code_pca_raster(const double* X, int64_t n_rows, const double* axis_limits, const uint8_t* table, int table_len, int H, int W,
+                        int margin, int marker_px, uint32_t* counts, int64_t counts_elems, uint8_t* out, int64_t out_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

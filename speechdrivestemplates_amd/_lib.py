@@ -125,6 +125,11 @@ SIGNATURES = {
     "sdt_speaker_stats_state_bytes": [_i, _i],  # (returns int64_t: restype set in load())
     "sdt_speaker_stats_accumulate": [_i, _i, _p, _i64, _i64, _i, _i, _i, _i64, _i64, _p, _p, _i64, _p],
     "sdt_speaker_stats_finalize": [_i, _p, _i64, _i, _i, _p, _p, _p, _p, _p, _p],
+    "sdt_code_pca_workspace_bytes": [_i64, _i],  # (returns int64_t: restype set in load())
+    "sdt_code_pca_moments": [_p, _i64, _i, _p, _i64, _p, _p, _p, _p],
+    "sdt_code_pca_eigh": [_p, _i, _i, C.c_double, _p, _p, _p, _p, _p],
+    "sdt_code_pca_project": [_p, _i64, _i, _p, _p, _p, _p, _i64, _p, _p],
+    "sdt_code_pca_raster": [_p, _i64, _p, _p, _i, _i, _i, _i, _i, _p, _i64, _p, _i64, _p],
 }
 F32, BF16 = 0, 1  # enum sdt_dtype
 
@@ -168,6 +173,7 @@ def load():
         fn.restype = C.c_int
     lib.sdt_render_workspace_bytes.restype = C.c_int64
     lib.sdt_speaker_stats_state_bytes.restype = C.c_int64
+    lib.sdt_code_pca_workspace_bytes.restype = C.c_int64
     lib.sdt_conv_dw_group_plan_bytes.argtypes = [_i]
     lib.sdt_conv_dw_group_plan_bytes.restype = C.c_int64
     lib.sdt_conv_dw_workspace_bytes.argtypes = [_G]

@@ -52,6 +52,10 @@ _DEFAULTS = {
             # RENDER_VIDEO True = TRAIN/TEST.SAVE_VIDEO and the demo write the reference's videos and long images, drawn on the GPU
             # (render.py, video.py; mp4 needs an ffmpeg executable, else the JPEG frames + wav are kept).  False = npz output only.
             "RENDER_VIDEO": False,
+            # EPOCH_FIGURES True = at the end of every epoch the master process writes <base>/figures/epoch<E>-clip_code.png, the reference's
+            # train/clip_code figure (a 2-component PCA of the clip-code table, scatter-plotted), computed and drawn on the GPU (code_pca.py;
+            # DESIGN.md section 12) and logs its explained-variance ratios and axis limits.  False = no figure, the loop as it was.
+            "EPOCH_FIGURES": False,
             # CONV_F32_SPLIT (fp32 tensors): Conv2d products as six bf16 MFMA products of an exact three-way bf16 split of both operands, fp32
             # accumulation (csrc/convbf.hip; fp32-grade results, 1.3x faster); False = the fp32-MFMA kernels of rounds 3-4
             "CONV_F32_SPLIT": True,

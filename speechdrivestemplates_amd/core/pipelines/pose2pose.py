@@ -90,6 +90,12 @@ class Pose2Pose(Trainer):
             ops.flush_deferred_dw()
         return losses, results
 
+    def draw_figure_epoch(self):
+        """the per-clip code means written by the train steps, projected on their two principal axes (pose2pose.py:314-345)"""
+        if self.cfg.POSE2POSE.AUTOENCODER.CODE_DIM is None:
+            return {}
+        return self._clip_code_figure(self.model.clip_code_mu)
+
     def optimizer_updates(self, losses):
         opt = self.optimizers['optimizer']
         self.reducer.all_reduce([opt])

@@ -2,7 +2,8 @@
 dataloader setup (:64-145), experiment setup with resume / pretrain (:162-224), step logging (:242-263),
 checkpoint wire format (:305-321), epoch loop (:367-405) and validation (:407-427).  TensorBoard output of the
 reference is out of scope; scalars go to the Python logger.  Pose videos and long images are drawn on
-the GPU (render.py) and written by video.VideoWriter when SYS.RENDER_VIDEO is set (opt-in; default: npz only)."""
+the GPU (render.py) and written by video.VideoWriter when SYS.RENDER_VIDEO is set (opt-in; default: npz only).  The per-epoch
+clip-code figure (:404-405, 281-283) is drawn on the GPU (code_pca.py) and written as a PNG when SYS.EPOCH_FIGURES is set."""
 import logging
 import os
 import time
@@ -217,6 +218,34 @@ class Trainer(object):
         self.setup_video_writer().save_video(self.cfg, 'DEMO', vid_batch, t_step, epoch, long_img=long_img,
                                              audio=None if audio is None else audio[0], base_path=self.base_path, extra_id=extra_id)
 
+    # -- epoch figures (trainer.py:227-231,404-405; voice2pose.py:479-510; pose2pose.py:314-345) --------------------------------
+    def draw_figure_epoch(self):
+        """{name: (H, W, 3) uint8 RGB device image} drawn at the end of an epoch; a pipeline that draws also leaves
+        ``self.figure_meta[name]`` (the numbers a figure with axes would show).  The base pipeline draws nothing (trainer.py:227-231)."""
+        return {}
+
+    def _clip_code_figure(self, codes):
+        from ... import code_pca
+        image, meta = code_pca.clip_code_figure(codes.detach(), return_meta=True)
+        self.figure_meta = {'clip_code': meta}
+        return {'clip_code': image}
+
+    def write_epoch_figures(self, epoch):
+        """SYS.EPOCH_FIGURES, master process, end of an epoch: <base>/figures/epoch<E>-<name>.png and one log line (the reference hands
+        the figures to TensorBoard, trainer.py:281-283).  Eager launches on the current stream, between steps; no collective."""
+        from ... import code_pca
+        try:
+            figures = self.draw_figure_epoch()
+        except ValueError as e:  # the TABLE cannot be drawn (a non-finite entry, all rows equal): say so and go on training
+            logging.error('[TRAIN] epoch plotting: no figure for epoch %d: %s' % (epoch, e))
+            return
+        msg = '[TRAIN] epoch plotting: '
+        for name, image in figures.items():
+            meta = getattr(self, 'figure_meta', {}).get(name)
+            code_pca.save_png(os.path.join(self.base_path, 'figures', 'epoch%d-%s.png' % (epoch, name)), image, meta)
+            msg += '%s, %s  ' % (name.replace('_', ' ').title(), code_pca.describe(meta) if meta else '')
+        logging.info(msg)
+
     def _set_reducer(self, reducer):
         self.close()  # a second setup_optimizer on this pipeline: the old reducer's reserve goes back first
         self.reducer = reducer
@@ -305,6 +334,8 @@ class Trainer(object):
                 s.step()
             if self.is_master_process():
                 logging.info('[TRAIN] epoch_time: %.2f hours' % ((time.time() - tic) / 3600))
+                if getattr(self.cfg.SYS, 'EPOCH_FIGURES', False):
+                    self.write_epoch_figures(epoch + 1)  # (trainer.py:404-405)
 
     @torch.no_grad()
     def validate(self, test_dataloader=None, epoch=0):

@@ -377,6 +377,13 @@ class Voice2Pose(Trainer):
             self.write_demo_video(results['poses_pred_batch'][0], t_step, epoch, batch['audio'], extra_id)
         return results
 
+    def draw_figure_epoch(self):
+        """the clip-code table (learned, or the external codes of sdt_vae) projected on its two principal axes (voice2pose.py:479-510)"""
+        if self.cfg.VOICE2POSE.GENERATOR.CLIP_CODE.DIMENSION is None:
+            return {}
+        assert self.model.clips_code is not None
+        return self._clip_code_figure(self.model._code_table(self.model._device()))
+
     def evaluate_step(self, results_dict):
         """L2 distance and normalised lip-sync error (voice2pose.py:412-430) on final (de-normalised) poses."""
         p, g = results_dict['poses_pred_batch'], results_dict['poses_gt_batch']
