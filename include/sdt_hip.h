@@ -518,6 +518,35 @@ int sdt_code_pca_project(const float* x, int64_t n_rows, int dim, const double* 
 int sdt_code_pca_raster(const double* X, int64_t n_rows, const double* axis_limits, const uint8_t* table, int table_len, int H, int W,
                         int margin, int marker_px, uint32_t* counts, int64_t counts_elems, uint8_t* out, int64_t out_bytes, void* stream);
 
+/*
+ * The epoch-level validation metric, the Frechet gesture distance (core/utils/fgd.py:6-64, called from voice2pose.py:432-446; DESIGN.md
+ * section 13 is the contract).  A feature row is row r of the fp32 (rows, d0) tensor x0 followed by row r of the fp32 (rows, d1) tensor
+ * x1 (x1 NULL with d1 = 0); dim = d0 + d1, 2 <= dim <= 64.  All arithmetic is float64.  No allocation; every pointer except the two
+ * state-pointer arrays of finalize (host arrays, read during the call) is a device buffer; every size is checked before the launch.
+ *   state: sdt_fgd_state_bytes(dim) bytes (0: unsupported dim), 8-byte aligned, ZEROED by the caller once (and again to reset it).  In 8-byte
+ *     words: rows (int64) | 1 + the first non-finite row, 0 if none (int64) | shift (dim) | sums of x - shift (dim) | upper triangle of the
+ *     sums of (x - shift)(x - shift)^T, row-major (dim (dim + 1) / 2).  The shift is the first row the state ever sees (a non-finite entry
+ *     of it: 0).
+ *   accumulate: adds `rows` rows (1 <= rows <= 2^30) to a state, one workgroup, the rows in ascending order per entry: the state does not
+ *     depend on how the rows were cut into calls, and equal call sequences give equal bits.  A non-finite value records
+ *     rows_seen_base + r of the first such row (the first record stays) and makes the sums non-finite; finalize reports it.
+ *   finalize: states_a / states_b are num_states (1..64) state pointers per side (one per rank after an all-gather), merged in index order
+ *     with the pairwise update of (n, mean, M2); states without rows are skipped.  On the leading dim_used x dim_used block
+ *     (2 <= dim_used <= dim), with mean and covariance as numpy's (ddof = 1):
+ *       C_A = V L V^T (cyclic Jacobi until off(A) <= rel_tol ||A||_F), S = V sqrt(max(L, 0)) V^T, mu = eig(sym(S C_B S)) (Jacobi again),
+ *       FGD = |mean_A - mean_B|^2 + tr C_A + tr C_B - 2 sum_i sqrt(max(mu_i, 0))   (not clamped at zero).
+ *     out (16 float64): FGD, |mean_A - mean_B|^2, tr C_A, tr C_B, sum_i sqrt(max(mu_i, 0)), rows of A, rows of B, sweeps and final
+ *     off-diagonal Frobenius norm of the first decomposition, the same of the second, the smallest eigenvalue of the first and of the second,
+ *     the first non-finite row of A and of B (-1: none), 0.  err[0]: bit 0 = a decomposition did not converge within max_sweeps (FGD is
+ *     the value reached), bit 1 = fewer than 2 rows on a side, bit 2 = a non-finite row was recorded; with bit 1 or 2 every float field but
+ *     the rows and the bad rows is NaN.
+ */
+int64_t sdt_fgd_state_bytes(int dim);
+int sdt_fgd_accumulate(const float* x0, int d0, const float* x1, int d1, int64_t rows, void* state, int64_t state_bytes,
+                       int64_t rows_seen_base, void* stream);
+int sdt_fgd_finalize(const void* const* states_a, const void* const* states_b, int num_states, int dim, int dim_used, int max_sweeps,
+                     double rel_tol, double* out, int32_t* err, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -56,6 +56,11 @@ _DEFAULTS = {
             # train/clip_code figure (a 2-component PCA of the clip-code table, scatter-plotted), computed and drawn on the GPU (code_pca.py;
             # DESIGN.md section 12) and logs its explained-variance ratios and axis limits.  False = no figure, the loop as it was.
             "EPOCH_FIGURES": False,
+            # DEVICE_FGD True = validate() / test() keep the pose-encoder features on the GPU: every test_step adds its rows to a float64 state of
+            # moments (fgd.FGDAccumulator, csrc/fgd.hip) instead of copying them to the host, and FGD_mu / FGD_mu_logvar come from
+            # the states of ALL ranks (one all-gather): the value of the whole validation set on every rank, whatever the world size.  False = the
+            # reference's loop: host copies per step, scipy sqrtm on the master's shard.
+            "DEVICE_FGD": False,
             # CONV_F32_SPLIT (fp32 tensors): Conv2d products as six bf16 MFMA products of an exact three-way bf16 split of both operands, fp32
             # accumulation (csrc/convbf.hip; fp32-grade results, 1.3x faster); False = the fp32-MFMA kernels of rounds 3-4
             "CONV_F32_SPLIT": True,

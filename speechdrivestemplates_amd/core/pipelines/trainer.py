@@ -308,6 +308,10 @@ class Trainer(object):
     def evaluate_epoch(self, results_dict):
         return {}
 
+    def uses_device_fgd(self):
+        """SYS.DEVICE_FGD and a pipeline that has an epoch-level FGD (Voice2Pose with a pose encoder)"""
+        return False
+
     # -- loops (trainer.py:367-427) ----------------------------------------------------------------------
     def train(self, cfg, exp_tag, resume_from=None):
         """``pipeline.train(cfg, exp_tag, args.resume_from)`` as main.py:51 calls it (trainer.py:367).  ``cfg`` is the object
@@ -350,6 +354,9 @@ class Trainer(object):
         self.model.eval()
         tic = time.time()
         sums, coll = {}, {}
+        device_fgd = self.uses_device_fgd()
+        if device_fgd and self.device_fgd() is not None:
+            self.device_fgd().reset()
         for t_step, batch in enumerate(test_dataloader):
             losses, res = self.test_step(batch, t_step + 1, epoch)
             for k, v in losses.items():
@@ -358,7 +365,9 @@ class Trainer(object):
                 coll.setdefault(k, []).append(v)
         self.check_kernels_all_ranks()
         out = {k: v / self.num_test_samples for k, v in sums.items()}
-        if coll and self.is_master_process():
+        if device_fgd:  # every rank takes part in the all-gather of the moment states and gets the whole set's value
+            out.update(self.evaluate_epoch_device())
+        elif coll and self.is_master_process():
             out.update(self.evaluate_epoch({k: np.concatenate(v, axis=0) for k, v in coll.items()}))
         if self.is_master_process():
             logging.info('[VAL] epoch: %d  val_time: %.1f min  ' % (epoch, (time.time() - tic) / 60) +

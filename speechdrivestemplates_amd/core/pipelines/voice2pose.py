@@ -10,6 +10,7 @@ Deliberate, documented differences from the reference:
     SYS.DDP_UNSYNCED_D reproduces that);
   * per-loss scalars are reduced to rank 0 in one packed collective, only on logging steps.
 """
+import logging
 from collections import OrderedDict
 
 import torch
@@ -358,6 +359,10 @@ class Voice2Pose(Trainer):
             if t_step % self.result_saving_interval_test == 0 and self.cfg.TEST.SAVE_VIDEO and self.rendering() and self.base_path is not None:
                 self.write_pair_video(tag, fin_p[0], fin_g[0], t_step, epoch, audio=batch['audio'])  # voice2pose.py:372-378
         batch_losses = {k: v.detach() * self.cfg.TEST.BATCH_SIZE for k, v in losses.items()}
+        if self.uses_device_fgd():  # SYS.DEVICE_FGD: the features go into the moment states on the device, nothing goes to the host
+            ops.join_side_stream()
+            self.device_fgd(results['mu_pred']).add(results['mu_pred'], results['mu_gt'], results['logvar_pred'], results['logvar_gt'])
+            return batch_losses, {}
         keep = ('mu_pred', 'mu_gt', 'logvar_pred', 'logvar_gt', 'condition_code')
         return batch_losses, {k: v.detach().cpu().numpy() for k, v in results.items() if k in keep and v is not None}
 
@@ -392,6 +397,36 @@ class Voice2Pose(Trainer):
         lg = torch.norm(g[:, :, :, 75] - g[:, :, :, 71], p=2, dim=-1)
         den = lg.max(-1, keepdim=True).values + 1e-4
         return {'L2_dist': l2.mean(), 'lip_sync_error_n': torch.abs(lp / den - lg / den).mean()}
+
+    def uses_device_fgd(self):
+        return bool(getattr(self.cfg.SYS, 'DEVICE_FGD', False)) and self.cfg.VOICE2POSE.POSE_ENCODER.NAME is not None
+
+    def device_fgd(self, mu=None):
+        """the accumulator of mu ++ logvar rows (created at the first step, which knows the code width and the device)"""
+        if getattr(self, '_device_fgd', None) is None and mu is not None:
+            from ...fgd import FGDAccumulator
+            self._device_fgd = FGDAccumulator(2 * mu.shape[1], mu.device)
+        return getattr(self, '_device_fgd', None)
+
+    def evaluate_epoch_device(self):
+        """FGD_mu (the leading block of the mu ++ logvar moments) and FGD_mu_logvar over the rows every rank delivered: the ranks' states are
+        all-gathered and merged in rank order, so every rank reports the same value.  A non-finite feature is a warning and a NaN metric,
+        not the end of a training run."""
+        from ...fgd import describe_error
+        acc = self.device_fgd()
+        if acc is None:  # no validation step ran
+            return {}
+        gathered = None
+        if self.cfg.SYS.DISTRIBUTED:
+            gathered = [torch.empty_like(acc.states()) for _ in range(torch.distributed.get_world_size())]
+            torch.distributed.all_gather(gathered, acc.states())  # (the list form: nccl and gloo both have it)
+        out = {}
+        for key, dim_used in (('FGD_mu', acc.dim // 2), ('FGD_mu_logvar', acc.dim)):
+            res = acc.result(dim_used=dim_used, gathered=gathered, strict=False)
+            if res['err']:
+                logging.warning('[VAL] %s: %s' % (key, describe_error(res)))
+            out[key] = res['fgd']
+        return out
 
     def evaluate_epoch(self, results_dict):
         from ...fgd import compute_fgd
