@@ -547,6 +547,38 @@ int sdt_fgd_accumulate(const float* x0, int d0, const float* x1, int d1, int64_t
 int sdt_fgd_finalize(const void* const* states_a, const void* const* states_b, int num_states, int dim, int dim_used, int max_sweeps,
                      double rel_tol, double* out, int32_t* err, void* stream);
 
+/*
+ * Baseline JPEG encoding of the renderer's frames (DESIGN.md section 14 is the contract; integer arithmetic only, a host model
+ * reproduces the bytes).  frames: (n, H, W, 3) uint8 BGR, any 1 <= n, H, W <= 65535.  The stream is SOF0, YCbCr 4:2:0, one scan, one
+ * restart interval per MCU row (ceil(W / 16) MCUs), DC prediction reset per interval.  The library writes the entropy-coded part only:
+ * for image i the bytes [offsets[i * rows], offsets[(i + 1) * rows]) of `out`, rows = ceil(H / 16), are everything that follows the SOS
+ * header: the intervals, each padded with 1-bits to a byte and with 0x00 stuffed after every 0xFF, RST0..7 cycling between them, and EOI.
+ * The caller writes the headers and owns the tables they announce:
+ *   tables (SDT_JPEG_TABLE_WORDS uint32, device): 64 luminance then 64 chrominance quantisation values (1..255, clamped) in natural
+ *     (row-major) order | 16 DC luminance | 16 DC chrominance | 256 AC luminance | 256 AC chrominance Huffman entries, indexed by symbol,
+ *     each code | length << 16 (length <= 16, clamped; 0 = no code).
+ *   colour:  Y = (19595 R + 38470 G + 7471 B + 32768) >> 16, Cb = (-11059 R - 21709 G + 32768 B + (128 << 16) + 32767) >> 16,
+ *     Cr = (32768 R - 27439 G - 5329 B + (128 << 16) + 32767) >> 16 (arithmetic shifts); the last row and column are repeated up to a
+ *     multiple of 16; chroma = (a + b + c + d + bias) >> 2 over 2 x 2 with bias 1, 2, 1, 2, ... along the output columns.
+ *   transform: level shift -128, the 13-bit LLM integer forward DCT (rows with 2 extra bits, then columns; outputs carry a factor 8),
+ *     quantised as sign(c) * ((|c| + 4 q) / (8 q)).
+ * measure = transform + the exact byte length of every interval + their exclusive prefix sum: offsets (intervals + 1 int64, device),
+ *   offsets[intervals] = the total.  pack writes the bytes; it needs the workspace measure left and out_bytes >= the total.
+ * workspace: sdt_jpeg_workspace_bytes(n, H, W) bytes (0: unsupported sizes), 16-byte aligned, written before it is read.
+ * err (device int32; measure zeroes it): SDT_JPEG_ERR_STAGE = one MCU's codes exceed the staging buffer (only with a malformed table),
+ *   SDT_JPEG_ERR_RANGE = pack met a byte position outside its interval's range (offsets not from measure on the same input); nothing
+ *   is written outside `out` in either case.  No allocation; every index is checked against the sizes given.
+ */
+#define SDT_JPEG_TABLE_WORDS 672
+#define SDT_JPEG_ERR_STAGE 1
+#define SDT_JPEG_ERR_RANGE 2
+int64_t sdt_jpeg_workspace_bytes(int n, int H, int W);
+int64_t sdt_jpeg_intervals(int n, int H, int W);
+int sdt_jpeg_measure(const uint8_t* frames, int64_t frames_bytes, int n, int H, int W, const uint32_t* tables, void* workspace,
+                     int64_t workspace_bytes, int64_t* offsets, int64_t offsets_elems, int32_t* err, void* stream);
+int sdt_jpeg_pack(const void* workspace, int64_t workspace_bytes, int n, int H, int W, const uint32_t* tables, const int64_t* offsets,
+                  int64_t offsets_elems, uint8_t* out, int64_t out_bytes, int32_t* err, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -52,6 +52,11 @@ _DEFAULTS = {
             # RENDER_VIDEO True = TRAIN/TEST.SAVE_VIDEO and the demo write the reference's videos and long images, drawn on the GPU
             # (render.py, video.py; mp4 needs an ffmpeg executable, else the JPEG frames + wav are kept).  False = npz output only.
             "RENDER_VIDEO": False,
+            # DEVICE_JPEG True = the video writer takes the JPEG frames of 'mp4' and the long image of 'img' from the GPU encoder (jpeg.py,
+            # csrc/jpeg.hip) whenever the pictures are device tensors: only compressed bytes are copied to the host.
+            # False = raw frames are copied and PIL encodes them.  VIDEO_FORMAT also takes 'avi' (not in the default list): a Motion-JPEG
+            # file with PCM audio that needs no ffmpeg (avi.py); its device frames always go through the GPU encoder.
+            "DEVICE_JPEG": False,
             # EPOCH_FIGURES True = at the end of every epoch the master process writes <base>/figures/epoch<E>-clip_code.png, the reference's
             # train/clip_code figure (a 2-component PCA of the clip-code table, scatter-plotted), computed and drawn on the GPU (code_pca.py;
             # DESIGN.md section 12) and logs its explained-variance ratios and axis limits.  False = no figure, the loop as it was.

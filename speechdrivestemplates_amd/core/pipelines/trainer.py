@@ -187,7 +187,8 @@ class Trainer(object):
 
     # -- videos (trainer.py:374,437,467; voice2pose.py:318-331,372-378,404-410,448-459) -----------------------------------
     def rendering(self):
-        """SYS.RENDER_VIDEO: TRAIN/TEST.SAVE_VIDEO and the demo write videos / long images (drawn on the GPU)"""
+        """SYS.RENDER_VIDEO: TRAIN/TEST.SAVE_VIDEO and the demo write videos / long images (drawn on the GPU; the writer encodes them on the
+        GPU too with SYS.DEVICE_JPEG or the 'avi' token of SYS.VIDEO_FORMAT, video.py)"""
         return bool(getattr(self.cfg.SYS, 'RENDER_VIDEO', False))
 
     def setup_video_writer(self):

@@ -5,12 +5,17 @@ semantics, fed by the GPU renderer (render.py).
                 executable on PATH is called with an argument list (no ffmpeg-python).  Without one, the %06d.jpg frames stay in
                 <base>/videos/epoch<E>-<TAG>-step<S>[-<id>]/ next to the wav and this is logged once.
   'img'         <base>/imgs/epoch<E>-DEMO-step<S>[-<id>].jpg, the long image, DEMO only, JPEG quality 95 (cv2.imwrite's default).
+  'avi'         <base>/videos/epoch<E>-<TAG>-step<S>[-<id>].avi, Motion-JPEG with the clip's audio as PCM (avi.py): needs no ffmpeg.
+                Not in the default list.  Device frames are encoded on the GPU (jpeg.py), numpy frames with PIL.
   'tensorboard' not available in this engine: warned once and skipped.
 
 Frames arrive as (T, H, W, 3) uint8 BGR device tensors (or numpy arrays); the device -> host copy goes through pinned memory, and
-the JPEGs are written from RGB (PIL).  SYS.ASYNC_VIDEO_SAVING: one worker thread encodes, ``close()`` drains it.
-``last_timing`` holds the seconds of the last save's device -> host copy and encode.
+the JPEGs are written from RGB (PIL).  With SYS.DEVICE_JPEG, device frames and the device long image are encoded to JPEG on the GPU
+(jpeg.encode_frames): only compressed bytes are copied and the writers below only write files; numpy frames
+keep the PIL route.  SYS.ASYNC_VIDEO_SAVING: one worker thread encodes, ``close()`` drains it.
+``last_timing`` holds the seconds of the last save's device -> host copy (with SYS.DEVICE_JPEG: GPU encode + compressed copy) and encode.
 """
+import io
 import logging
 import os
 import queue
@@ -60,6 +65,33 @@ def write_jpg(path, bgr, quality=95):
     Image.fromarray(np.ascontiguousarray(bgr[..., ::-1])).save(path, quality=quality)
 
 
+def _jpg_bytes(bgr, quality=95):
+    """write_jpg's file, in memory"""
+    from PIL import Image
+    buf = io.BytesIO()
+    Image.fromarray(np.ascontiguousarray(bgr[..., ::-1])).save(buf, 'JPEG', quality=quality)
+    return buf.getvalue()
+
+
+def _on_device(x):
+    return torch.is_tensor(x) and x.is_cuda
+
+
+def _device_jpegs(x, quality=95):
+    """device frames (T, H, W, 3) or one image (H, W, 3) -> list of complete JPEG files, encoded on the GPU"""
+    from . import jpeg
+    return jpeg.encode_frames(x.contiguous(), quality)
+
+
+def _put_jpg(path, frame):
+    """``frame``: a BGR array (PIL route) or an already encoded file (SYS.DEVICE_JPEG)"""
+    if isinstance(frame, bytes):
+        with open(path, 'wb') as f:
+            f.write(frame)
+    else:
+        write_jpg(path, frame)
+
+
 class VideoWriter(object):
     def __init__(self, cfg) -> None:
         super().__init__()
@@ -103,12 +135,24 @@ class VideoWriter(object):
         formats = cfg.SYS.VIDEO_FORMAT
         if 'tensorboard' in formats:
             _log_once('tensorboard', 'SYS.VIDEO_FORMAT: tensorboard output is not provided by this engine; skipped')
+        device_jpeg = bool(getattr(cfg.SYS, 'DEVICE_JPEG', False))
         tic = time.time()
-        frames_h = to_host(frames) if 'mp4' in formats and frames is not None else None
-        long_h = to_host(long_img) if 'img' in formats and long_img is not None and tag == 'DEMO' else None
+        frames_h = long_h = avi_frames = None
+        jpegs = None  # the frames as JPEG files from the GPU encoder, shared by 'mp4' (SYS.DEVICE_JPEG) and 'avi'
+        if frames is not None and _on_device(frames) and (('mp4' in formats and device_jpeg) or 'avi' in formats):
+            jpegs = _device_jpegs(frames)
+        if 'mp4' in formats and frames is not None:
+            frames_h = jpegs if jpegs is not None and device_jpeg else to_host(frames)
+        if 'avi' in formats and frames is not None:
+            avi_frames = jpegs if jpegs is not None else (frames_h if frames_h is not None else to_host(frames))
+        if 'img' in formats and long_img is not None and tag == 'DEMO':
+            long_h = _device_jpegs(long_img)[0] if device_jpeg and _on_device(long_img) else to_host(long_img)
         self.last_timing = {'d2h': time.time() - tic}
         if frames_h is not None:
             self._run(self.save_video_in_mp4, (cfg, tag, frames_h, step, epoch, global_step, _audio_np(audio), base_path, extra_id), cfg)
+        if avi_frames is not None:
+            size = (int(frames.shape[1]), int(frames.shape[2]))
+            self._run(self.save_video_in_avi, (cfg, tag, avi_frames, size, step, epoch, global_step, _audio_np(audio), base_path, extra_id), cfg)
         if 'img' in formats:
             self._run(self.save_video_in_long_img, (cfg, tag, long_h, step, epoch, global_step, base_path, extra_id), cfg)
 
@@ -121,10 +165,23 @@ class VideoWriter(object):
         img_path = os.path.join(img_dir, _stem(epoch, tag, step, extra_id) + '.jpg')
         if os.path.exists(img_path):
             os.remove(img_path)
-        write_jpg(img_path, long_img)
+        _put_jpg(img_path, long_img)
         vid_toc = time.time() - vid_tic
         self.last_timing['encode_img'] = vid_toc
         logging.info('[%s] epoch: %d/%d  step: %s  Saved %s in %.3f seconds.' % (tag, epoch, cfg.TRAIN.NUM_EPOCHS, step, 'long image', vid_toc))
+
+    def save_video_in_avi(self, cfg, tag, frames, size, step, epoch, global_step, audio, base_path, extra_id=None):
+        """``frames``: JPEG files from the GPU encoder, or a (T, H, W, 3) BGR array that PIL encodes here; ``size`` = (H, W)"""
+        from . import avi
+        vid_tic = time.time()
+        vid_dir = os.path.join(base_path, 'videos')
+        os.makedirs(vid_dir, exist_ok=True)
+        jpegs = [frame if isinstance(frame, bytes) else _jpg_bytes(frame) for frame in frames]
+        vid_path = os.path.join(vid_dir, _stem(epoch, tag, step, extra_id) + '.avi')
+        avi.write_avi(vid_path, jpegs, cfg.DATASET.FPS, size[1], size[0], audio=audio, sample_rate=cfg.DATASET.AUDIO_SR)
+        vid_toc = time.time() - vid_tic
+        self.last_timing['encode_avi'] = vid_toc
+        logging.info('[%s] epoch: %d/%d  step: %s  Saved %s videos in %.3f seconds.' % (tag, epoch, cfg.TRAIN.NUM_EPOCHS, step, 'avi', vid_toc))
 
     def save_video_in_mp4(self, cfg, tag, frames, step, epoch, global_step, audio, base_path, extra_id=None):
         vid_tic = time.time()
@@ -134,7 +191,7 @@ class VideoWriter(object):
         frame_dir = os.path.join(vid_dir, 'tmp', '%f' % time.time()) if ffmpeg else os.path.join(vid_dir, stem)
         os.makedirs(frame_dir, exist_ok=True)
         for idx, frame in enumerate(frames):
-            write_jpg(os.path.join(frame_dir, '%06d.jpg' % idx), frame)
+            _put_jpg(os.path.join(frame_dir, '%06d.jpg' % idx), frame)
         wav_path = None
         if audio is not None:
             from scipy.io.wavfile import write
