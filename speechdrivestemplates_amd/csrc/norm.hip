@@ -58,6 +58,12 @@ __global__ __launch_bounds__(256) void colstats_kernel(const TA* __restrict__ a,
         const int64_t r1 = min(R, r0 + rows_per_block);
         const size_t base = (size_t)g * R * C + 4 * cv;
         f32x4 s = {0.f, 0.f, 0.f, 0.f}, q = {0.f, 0.f, 0.f, 0.f};
+        // Forward statistics over at most UNR rows (uniform branch): sums and squares in fp64, where an fp32 x fp32 product is exact.  The
+        // one-pass variance q/R - m^2 with fp32 squares carries 2^-24 (1 + (mean/std)^2) of relative error, and with two to four samples
+        // the sample std is often a small fraction of the mean (P(std < sigma/k) ~ k^-(R-1): certain among 1024 channels of pairs,
+        // ~1e-7 from five rows on): two rows 0.1 apart around 5 lost three digits of the output.  More rows keep the fp32 partials.
+        const bool few = !BWD && R <= UNR;
+        double sd[4] = {0.0, 0.0, 0.0, 0.0}, qd[4] = {0.0, 0.0, 0.0, 0.0};
         f32x4 mu = {0.f, 0.f, 0.f, 0.f}, rs = mu, ga = {1.f, 1.f, 1.f, 1.f}, be = {0.f, 0.f, 0.f, 0.f};
         if constexpr (BWD) {
             mu = *(const f32x4*)(mean + (size_t)g * C + 4 * cv);
@@ -79,8 +85,17 @@ __global__ __launch_bounds__(256) void colstats_kernel(const TA* __restrict__ a,
 #pragma unroll
             for (int j = 0; j < UNR; ++j) {
                 if constexpr (!BWD) {
-                    s += v[j];
-                    q += v[j] * v[j];
+                    if (few) {
+#pragma unroll
+                        for (int e = 0; e < 4; ++e) {
+                            const double dv = (double)v[j][e];
+                            sd[e] += dv;
+                            qd[e] += dv * dv;
+                        }
+                    } else {
+                        s += v[j];
+                        q += v[j] * v[j];
+                    }
                 } else {
 #pragma unroll
                     for (int e = 0; e < 4; ++e) {
@@ -94,8 +109,8 @@ __global__ __launch_bounds__(256) void colstats_kernel(const TA* __restrict__ a,
         }
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
-            atomicAdd(&sS[4 * cv + e], (double)s[e]);
-            atomicAdd(&sQ[4 * cv + e], (double)q[e]);
+            atomicAdd(&sS[4 * cv + e], few ? sd[e] : (double)s[e]);
+            atomicAdd(&sQ[4 * cv + e], few ? qd[e] : (double)q[e]);
         }
     }
     __syncthreads();
@@ -291,7 +306,10 @@ __global__ __launch_bounds__(256) void rownorm_kernel(const float* __restrict__ 
         float s = 0.f;
 #pragma unroll
         for (int i = 0; i < NV; ++i) s += (v[i][0] + v[i][1]) + (v[i][2] + v[i][3]);
-        const float mu = wave_sum(s) * invC;
+        // divided, not multiplied by 1/C (inexact unless C is a power of two): whenever the fp32 sum of C equal values is exact (-0.75 x 1020),
+        // their mean is that value, and the constant row normalises to exactly 0 instead of +-1 ulp * rstd on a random side of the
+        // activation's kink.  A constant whose sum rounds (0.1 x 1020) can still miss by an ulp.
+        const float mu = wave_sum(s) / (float)C;
         float q = 0.f;
 #pragma unroll
         for (int i = 0; i < NV; ++i)

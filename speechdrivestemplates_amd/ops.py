@@ -1572,6 +1572,9 @@ class ResizeConcatFn(torch.autograd.Function):
         lib = _lib.load()
         x_cl = x_cl.contiguous()
         B, H, W, C = x_cl.shape
+        # resize_concat_fwd_kernel reads row b of ``code`` for clip b without a bound check: the shape is checked here
+        if code is not None and (code.dim() != 2 or code.shape[0] != B):
+            raise ValueError("ResizeConcatFn needs one code row per clip: code %s for %d clips" % (tuple(code.shape), B))
         D = 0 if code is None else code.shape[1]
         idx = None
         if code is not None:
