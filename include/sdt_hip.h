@@ -579,6 +579,41 @@ int sdt_jpeg_measure(const uint8_t* frames, int64_t frames_bytes, int n, int H, 
 int sdt_jpeg_pack(const void* workspace, int64_t workspace_bytes, int n, int H, int W, const uint32_t* tables, const int64_t* offsets,
                   int64_t offsets_elems, uint8_t* out, int64_t out_bytes, int32_t* err, void* stream);
 
+/*
+ * Animated-GIF encoding of the renderer's frames for the TensorBoard video summary (core/utils/video_processing.py:72-98; DESIGN.md
+ * section 15 is the contract; integer arithmetic only, gif.py's model_* functions reproduce the bytes).  frames: (n, H, W, 3) uint8 BGR.
+ *   downscale (F.interpolate(scale_factor=0.4, mode='area')): h = (2 H) / 5, w = (2 W) / 5 (or h = H, w = W: no downscale); output pixel
+ *     (i, j) = per channel (sum + cnt / 2) / cnt over source rows [floor(i H / h), ceil((i + 1) H / h)) and the same range of columns,
+ *     cnt = the number of source pixels in the window; channels swapped to RGB.
+ *   quantisation: bin = (R >> 3) << 10 | (G >> 3) << 5 | (B >> 3); one histogram over the clip (32-bit integer counts).  The palette is the
+ *     at most 256 most populated non-empty bins, ties at the cut won by the lower bin, listed in ascending bin order; a palette colour is
+ *     c5 << 3 | c5 >> 2 per channel, unused entries are 0.  Every bin maps to the palette entry with the smallest squared distance in
+ *     5-bit space, ties to the lower entry.
+ *   LZW (GIF89a, minimum code size 8: Clear 256, EOI 257, first free code 258, 9-bit start, LSB first): a row of a frame is one segment, or,
+ *     if w > 3838, parts = ceil(w / 3838) segments of ceil(w / parts) pixels, the last taking the rest.  A frame's stream is Clear at 9 bits,
+ *     then per segment its codes from an EMPTY table followed by Clear (after the frame's last segment: EOI) at the width the segment ended
+ *     in.  Code k of a segment (k = 0, 1, ...) is 9 + (k >= 255) + (k >= 767) + (k >= 1791) bits wide, and so is the code that follows a
+ *     segment of k codes.  Frames start on a byte; the last byte of a frame is padded with 0-bits.
+ * quantise writes rgb (n, h, w, 3; nullable), indices (n, h, w) and palette (256, 3).  measure codes every segment and writes offsets
+ *   (int64, device): [0 .. n] the byte offset of every frame's stream and the total, [n + 1 + s] the bit offset of the first code of segment
+ *   s = (frame * h + row) * parts + part.  pack zeroes out[0, out_bytes) and writes the streams; it needs the workspace measure left,
+ *   out 4-byte aligned and out_bytes a multiple of 4 that is >= the total.
+ * workspace: sdt_gif_workspace_bytes(n, h, w) bytes (0: unsupported sizes), 16-byte aligned, written before it is read; quantise and
+ *   measure / pack may share it (measure overwrites what quantise left).
+ * err (device int32; measure zeroes it): SDT_GIF_ERR_RANGE = pack met a bit outside its frame's byte range (offsets not from measure on the
+ *   same input): it is dropped; SDT_GIF_ERR_COUNT = a segment's code count in the workspace exceeds its length: the segment is skipped.
+ *   Nothing is written outside `out` in either case.  No allocation; every index is checked against the sizes given.
+ */
+#define SDT_GIF_ERR_RANGE 1
+#define SDT_GIF_ERR_COUNT 2
+int64_t sdt_gif_workspace_bytes(int n, int h, int w);
+int sdt_gif_quantise(const uint8_t* frames, int64_t frames_bytes, int n, int H, int W, int h, int w, uint8_t* rgb, int64_t rgb_bytes,
+                     uint8_t* indices, int64_t indices_bytes, uint8_t* palette, void* workspace, int64_t workspace_bytes, void* stream);
+int sdt_gif_measure(const uint8_t* indices, int64_t indices_bytes, int n, int h, int w, void* workspace, int64_t workspace_bytes,
+                    int64_t* offsets, int64_t offsets_elems, int32_t* err, void* stream);
+int sdt_gif_pack(const void* workspace, int64_t workspace_bytes, int n, int h, int w, const int64_t* offsets, int64_t offsets_elems,
+                 uint8_t* out, int64_t out_bytes, int32_t* err, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -137,6 +137,10 @@ SIGNATURES = {
     "sdt_jpeg_intervals": [_i, _i, _i],  # (returns int64_t: restype set in load())
     "sdt_jpeg_measure": [_p, _i64, _i, _i, _i, _p, _p, _i64, _p, _i64, _p, _p],
     "sdt_jpeg_pack": [_p, _i64, _i, _i, _i, _p, _p, _i64, _p, _i64, _p, _p],
+    "sdt_gif_workspace_bytes": [_i, _i, _i],  # (returns int64_t: restype set in load())
+    "sdt_gif_quantise": [_p, _i64, _i, _i, _i, _i, _i, _p, _i64, _p, _i64, _p, _p, _i64, _p],
+    "sdt_gif_measure": [_p, _i64, _i, _i, _i, _p, _i64, _p, _i64, _p, _p],
+    "sdt_gif_pack": [_p, _i64, _i, _i, _i, _p, _i64, _p, _i64, _p, _p],
 }
 F32, BF16 = 0, 1  # enum sdt_dtype
 
@@ -184,6 +188,7 @@ def load():
     lib.sdt_fgd_state_bytes.restype = C.c_int64
     lib.sdt_jpeg_workspace_bytes.restype = C.c_int64
     lib.sdt_jpeg_intervals.restype = C.c_int64
+    lib.sdt_gif_workspace_bytes.restype = C.c_int64
     lib.sdt_conv_dw_group_plan_bytes.argtypes = [_i]
     lib.sdt_conv_dw_group_plan_bytes.restype = C.c_int64
     lib.sdt_conv_dw_workspace_bytes.argtypes = [_G]

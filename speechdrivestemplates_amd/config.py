@@ -66,6 +66,11 @@ _DEFAULTS = {
             # the states of ALL ranks (one all-gather): the value of the whole validation set on every rank, whatever the world size.  False = the
             # reference's loop: host copies per step, scipy sqrtm on the master's shard.
             "DEVICE_FGD": False,
+            # TENSORBOARD True = the master process writes a TensorBoard event file into the run's directory (tb_events.py, no tensorboard
+            # package needed) with the reference's tags: train/lr_*, train/<loss>, train/epoch_time, train/ETA,
+            # train/<figure> (with EPOCH_FIGURES), val/<metric>, test/<metric>, and, with the 'tensorboard' token of VIDEO_FORMAT, the sample
+            # videos as animated GIFs that device frames get from the GPU encoder (gif.py, csrc/gif.hip).  False = no event file.
+            "TENSORBOARD": False,
             # CONV_F32_SPLIT (fp32 tensors): Conv2d products as six bf16 MFMA products of an exact three-way bf16 split of both operands, fp32
             # accumulation (csrc/convbf.hip; fp32-grade results, 1.3x faster); False = the fp32-MFMA kernels of rounds 3-4
             "CONV_F32_SPLIT": True,

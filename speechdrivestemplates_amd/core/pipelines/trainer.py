@@ -1,7 +1,7 @@
 """Training-loop shell around ``train_step`` (core/pipelines/trainer.py): rank helpers (:29-45), dataset /
 dataloader setup (:64-145), experiment setup with resume / pretrain (:162-224), step logging (:242-263),
-checkpoint wire format (:305-321), epoch loop (:367-405) and validation (:407-427).  TensorBoard output of the
-reference is out of scope; scalars go to the Python logger.  Pose videos and long images are drawn on
+checkpoint wire format (:305-321), epoch loop (:367-405) and validation (:407-427).  Scalars go to the Python logger and, with
+SYS.TENSORBOARD, to a TensorBoard event file under the reference's tags (tb_events.py; :242-303).  Pose videos and long images are drawn on
 the GPU (render.py) and written by video.VideoWriter when SYS.RENDER_VIDEO is set (opt-in; default: npz only).  The per-epoch
 clip-code figure (:404-405, 281-283) is drawn on the GPU (code_pca.py) and written as a PNG when SYS.EPOCH_FIGURES is set."""
 import logging
@@ -184,6 +184,10 @@ class Trainer(object):
         if vw is not None:
             vw.close()
             self.video_writer = None
+        tb = getattr(self, 'tb_writer', None)
+        if tb is not None:  # (after the video writer: its worker may still add a GIF)
+            tb.close()
+            self.tb_writer = None
 
     # -- videos (trainer.py:374,437,467; voice2pose.py:318-331,372-378,404-410,448-459) -----------------------------------
     def rendering(self):
@@ -196,6 +200,14 @@ class Trainer(object):
             from ...video import VideoWriter
             self.video_writer = VideoWriter(self.cfg)
         return getattr(self, 'video_writer', None)
+
+    def setup_tb_writer(self):
+        """SYS.TENSORBOARD, master process: one event file in the run's directory (trainer.py:373,436,466)"""
+        if getattr(self.cfg.SYS, 'TENSORBOARD', False) and self.is_master_process() and getattr(self, 'tb_writer', None) is None \
+                and self.base_path is not None:
+            from ...tb_events import EventWriter
+            self.tb_writer = EventWriter(self.base_path)
+        return getattr(self, 'tb_writer', None)
 
     def generate_video_pair(self, relative_poses_pred, relative_poses_gt):
         from ... import render
@@ -210,7 +222,8 @@ class Trainer(object):
         """clip 0's prediction beside its ground truth, with clip 0's audio (final poses, (T, 2, K))"""
         vid_batch = self.generate_video_pair(pred, gt)
         self.setup_video_writer().save_video(self.cfg, tag, vid_batch, t_step, epoch, global_step,
-                                             audio=None if audio is None else audio[0], base_path=self.base_path)
+                                             audio=None if audio is None else audio[0], writer=getattr(self, 'tb_writer', None),
+                                             base_path=self.base_path)
 
     def write_demo_video(self, pred, t_step, epoch, audio=None, extra_id=None):
         from ... import render
@@ -241,9 +254,13 @@ class Trainer(object):
             logging.error('[TRAIN] epoch plotting: no figure for epoch %d: %s' % (epoch, e))
             return
         msg = '[TRAIN] epoch plotting: '
+        tb = getattr(self, 'tb_writer', None)
         for name, image in figures.items():
             meta = getattr(self, 'figure_meta', {}).get(name)
-            code_pca.save_png(os.path.join(self.base_path, 'figures', 'epoch%d-%s.png' % (epoch, name)), image, meta)
+            path = code_pca.save_png(os.path.join(self.base_path, 'figures', 'epoch%d-%s.png' % (epoch, name)), image, meta)
+            if tb is not None:  # (trainer.py:281-283: add_figure stores a PNG image summary)
+                with open(path, 'rb') as f:
+                    tb.add_image_bytes('train/%s' % name, f.read(), int(image.shape[0]), int(image.shape[1]), epoch)
             msg += '%s, %s  ' % (name.replace('_', ' ').title(), code_pca.describe(meta) if meta else '')
         logging.info(msg)
 
@@ -299,6 +316,22 @@ class Trainer(object):
         vals = torch.stack([v.detach().double().reshape(()) for v in losses.values()]).cpu().tolist()  # one D2H copy
         msg += ''.join('%s: %.5f  ' % (k, x) for k, x in zip(losses.keys(), vals))
         logging.info(msg)
+        tb = getattr(self, 'tb_writer', None)
+        if tb is not None and tag == 'TRAIN':  # (trainer.py:250-263: the learning rate of every parameter group, then the losses)
+            for k, v in self.optimizers.items():
+                for i, group in enumerate(v.param_groups):
+                    tb.add_scalar('train/lr_%s' % k if i == 0 else 'train/lr_%s_%d' % (k, i), group['lr'], global_step)
+            for k, x in zip(losses.keys(), vals):
+                tb.add_scalar('train/%s' % k, x, global_step)
+            tb.flush()
+
+    def tb_epoch_scalars(self, prefix, values, epoch):
+        """SYS.TENSORBOARD: ``<prefix>/<k>`` at step = epoch (trainer.py:279-280, 291-294)"""
+        tb = getattr(self, 'tb_writer', None)
+        if tb is not None:
+            for k, v in values.items():
+                tb.add_scalar('%s/%s' % (prefix, k), float(v), epoch)
+            tb.flush()
 
     def train_step(self, batch, t_step, global_step, epoch):
         raise NotImplementedError
@@ -319,6 +352,7 @@ class Trainer(object):
         the pipeline was constructed with; like the reference, the loop reads ``self.cfg``."""
         self.base_path, epoch_start, global_step = self.setup_experiment(True, exp_tag, resume_from=resume_from)
         self.setup_video_writer()  # (trainer.py:374; only with SYS.RENDER_VIDEO, on the master process)
+        self.setup_tb_writer()  # (trainer.py:373; only with SYS.TENSORBOARD, on the master process)
         if self.cfg.SYS.DISTRIBUTED:
             torch.distributed.barrier()
         for epoch in range(epoch_start, self.cfg.TRAIN.NUM_EPOCHS):
@@ -338,12 +372,15 @@ class Trainer(object):
             for s in self.schedulers.values():
                 s.step()
             if self.is_master_process():
-                logging.info('[TRAIN] epoch_time: %.2f hours' % ((time.time() - tic) / 3600))
+                epoch_toc = (time.time() - tic) / 3600
+                logging.info('[TRAIN] epoch_time: %.2f hours' % epoch_toc)
+                # (trainer.py:399-402: the reference's mean runs over this epoch alone)
+                self.tb_epoch_scalars('train', {'epoch_time': epoch_toc, 'ETA': (self.cfg.TRAIN.NUM_EPOCHS - epoch - 1) * epoch_toc}, epoch + 1)
                 if getattr(self.cfg.SYS, 'EPOCH_FIGURES', False):
                     self.write_epoch_figures(epoch + 1)  # (trainer.py:404-405)
 
     @torch.no_grad()
-    def validate(self, test_dataloader=None, epoch=0):
+    def validate(self, test_dataloader=None, epoch=0, tag='VAL'):
         """trainer.py:407-427 (same positional signature).  Data-parallel runs first take rank 0's buffers (dp.sync_buffers):
         eval-mode BatchNorm then reads the same running statistics on every rank, as under DDP's per-forward buffer
         broadcast."""
@@ -373,13 +410,15 @@ class Trainer(object):
         if self.is_master_process():
             logging.info('[VAL] epoch: %d  val_time: %.1f min  ' % (epoch, (time.time() - tic) / 60) +
                          ''.join('%s: %.5f  ' % (k, float(v)) for k, v in out.items()))
+            self.tb_epoch_scalars(tag.lower(), out, epoch)  # (val/<k> from train(), test/<k> from test())
         return out
 
     def test(self, cfg, exp_tag, checkpoint):
         """``pipeline.test(cfg, exp_tag, args.checkpoint)`` (main.py:48, trainer.py:429)."""
         self.base_path = self.setup_experiment(False, exp_tag, checkpoint=checkpoint)
         self.setup_video_writer()
-        return self.validate(self.test_dataloader, 0)
+        self.setup_tb_writer()
+        return self.validate(self.test_dataloader, 0, tag='TEST')
 
     @torch.no_grad()
     def demo(self, cfg, exp_tag, checkpoint, demo_input):
@@ -388,6 +427,7 @@ class Trainer(object):
         videos / npz files)."""
         self.base_path = self.setup_experiment(False, exp_tag, checkpoint=checkpoint, demo_input=demo_input)
         self.setup_video_writer()
+        self.setup_tb_writer()
         self.model.eval()
         out = []
         for t_step, batch in enumerate(self.test_dataloader):

@@ -7,7 +7,11 @@ semantics, fed by the GPU renderer (render.py).
   'img'         <base>/imgs/epoch<E>-DEMO-step<S>[-<id>].jpg, the long image, DEMO only, JPEG quality 95 (cv2.imwrite's default).
   'avi'         <base>/videos/epoch<E>-<TAG>-step<S>[-<id>].avi, Motion-JPEG with the clip's audio as PCM (avi.py): needs no ffmpeg.
                 Not in the default list.  Device frames are encoded on the GPU (jpeg.py), numpy frames with PIL.
-  'tensorboard' not available in this engine: warned once and skipped.
+  'tensorboard' with a ``writer`` (tb_events.EventWriter; the Trainer passes its own when SYS.TENSORBOARD is set): the clip shrunk by 0.4 as an
+                animated GIF in an image summary, which is what the reference's ``add_video`` stores: tag ``train/video`` at global_step
+                for TRAIN, ``<tag>/video/<step>`` at the epoch for VAL / TEST, ``/<extra_id>`` appended; nothing for DEMO.  Device frames
+                are shrunk, quantised and LZW-coded on the GPU (gif.py), numpy frames by gif.model_downscale and
+                PIL.  Without a writer: warned once and skipped.
 
 Frames arrive as (T, H, W, 3) uint8 BGR device tensors (or numpy arrays); the device -> host copy goes through pinned memory, and
 the JPEGs are written from RGB (PIL).  With SYS.DEVICE_JPEG, device frames and the device long image are encoded to JPEG on the GPU
@@ -133,8 +137,8 @@ class VideoWriter(object):
     def save_video(self, cfg, tag, frames, step, epoch, global_step=None, long_img=None, audio=None, writer=None, base_path=None,
                    extra_id=None):
         formats = cfg.SYS.VIDEO_FORMAT
-        if 'tensorboard' in formats:
-            _log_once('tensorboard', 'SYS.VIDEO_FORMAT: tensorboard output is not provided by this engine; skipped')
+        if 'tensorboard' in formats and writer is None:
+            _log_once('tensorboard', 'SYS.VIDEO_FORMAT: tensorboard output needs an event writer (SYS.TENSORBOARD); skipped')
         device_jpeg = bool(getattr(cfg.SYS, 'DEVICE_JPEG', False))
         tic = time.time()
         frames_h = long_h = avi_frames = None
@@ -153,6 +157,14 @@ class VideoWriter(object):
         if avi_frames is not None:
             size = (int(frames.shape[1]), int(frames.shape[2]))
             self._run(self.save_video_in_avi, (cfg, tag, avi_frames, size, step, epoch, global_step, _audio_np(audio), base_path, extra_id), cfg)
+        if 'tensorboard' in formats and writer is not None and frames is not None and tag != 'DEMO':
+            if _on_device(frames):  # encoded here, on the caller's stream; the worker only appends the record
+                from . import gif
+                size = gif.out_size(int(frames.shape[1]), int(frames.shape[2]))
+                clip = gif.encode_gif(frames.contiguous(), cfg.DATASET.FPS)
+            else:
+                size, clip = None, frames_h if isinstance(frames_h, np.ndarray) else to_host(frames)
+            self._run(self.save_video_in_tensorboard, (cfg, tag, clip, size, step, epoch, global_step, writer, extra_id), cfg)
         if 'img' in formats:
             self._run(self.save_video_in_long_img, (cfg, tag, long_h, step, epoch, global_step, base_path, extra_id), cfg)
 
@@ -169,6 +181,36 @@ class VideoWriter(object):
         vid_toc = time.time() - vid_tic
         self.last_timing['encode_img'] = vid_toc
         logging.info('[%s] epoch: %d/%d  step: %s  Saved %s in %.3f seconds.' % (tag, epoch, cfg.TRAIN.NUM_EPOCHS, step, 'long image', vid_toc))
+
+    def save_video_in_tensorboard(self, cfg, tag, frames, size, step, epoch, global_step, writer, extra_id=None):
+        """``frames``: the GIF file from the GPU encoder with its ``size`` = (h, w), or a (T, H, W, 3) BGR array that is shrunk and
+        encoded here (core/utils/video_processing.py:72-98)"""
+        vid_tic = time.time()
+        if tag == 'TRAIN':
+            clip_tag, tb_step = 'train/video', global_step
+        elif tag in ('VAL', 'TEST'):
+            clip_tag, tb_step = '%s/video/%d' % (tag.lower(), step), epoch
+        elif tag == 'DEMO':
+            return
+        else:
+            raise Exception('Unknown tag: %s' % tag)
+        if extra_id is not None:
+            clip_tag += '/%s' % extra_id
+        if not isinstance(frames, bytes):
+            from PIL import Image
+
+            from . import gif
+            rgb = gif.model_downscale(frames)
+            size = rgb.shape[1:3]
+            images = [Image.fromarray(f) for f in rgb]
+            buf = io.BytesIO()
+            images[0].save(buf, 'GIF', save_all=True, append_images=images[1:], duration=int(round(1000.0 / cfg.DATASET.FPS)), loop=0)
+            frames = buf.getvalue()
+        writer.add_image_bytes(clip_tag, frames, int(size[0]), int(size[1]), 0 if tb_step is None else tb_step)
+        writer.flush()
+        vid_toc = time.time() - vid_tic
+        self.last_timing['encode_tensorboard'] = vid_toc
+        logging.info('[%s] epoch: %d/%d  step: %s  Saved %s videos in %.3f seconds.' % (tag, epoch, cfg.TRAIN.NUM_EPOCHS, step, 'tensorboard', vid_toc))
 
     def save_video_in_avi(self, cfg, tag, frames, size, step, epoch, global_step, audio, base_path, extra_id=None):
         """``frames``: JPEG files from the GPU encoder, or a (T, H, W, 3) BGR array that PIL encodes here; ``size`` = (H, W)"""
