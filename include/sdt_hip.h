@@ -614,6 +614,47 @@ int sdt_gif_measure(const uint8_t* indices, int64_t indices_bytes, int n, int h,
 int sdt_gif_pack(const void* workspace, int64_t workspace_bytes, int n, int h, int w, const int64_t* offsets, int64_t offsets_elems,
                  uint8_t* out, int64_t out_bytes, int32_t* err, void* stream);
 
+/*
+ * Clip preparation for a custom speaker (data_preprocess/2_2_remove_outlier.py, 2_3_rescale_shoulder_width.py and
+ * 3_1_generate_clips.py of the reference; DESIGN.md section 16 is the contract).  One video at a time: src is its (n_frames, 3, 137)
+ * keypoint array in float32 (elem_bytes 4) or float64 (8), present (n_frames uint8) marks the frames whose file exists.  Every
+ * floating-point operation is rounded on its own, nothing is accumulated with atomics: the same bits on every call.
+ *   frame_flags: keep[f] = present and no keypoint of 0, 2..7, 15, 16, 25..136 with x <= 3 and y <= 3 (compared in the element
+ *     type); dist[f] = sqrt((x2-x5)^2 + (y2-y5)^2) in float64 (0 for a dropped frame); bad[f] = a kept frame with a non-finite x / y.
+ *   scan: prefix (n_frames + 1 int32) = exclusive prefix sum of keep; dist_kept (n_frames) = the kept frames' dist, packed in order.
+ *   shoulder_means: means[c] = avg = avg*(num/(num+1)) + (1 - num/(num+1))*d over kept frames [c*stride, (c+1)*stride),
+ *     stride = prefix[n_frames] / chunks, in float64.
+ *   windows: starts = the s of range(start_frame, n_frames - num_frames, step) whose num_frames frames are all kept, ascending;
+ *     n_clips (device int32) their count.  sdt_clip_window_candidates = len(range(...)) is the capacity starts needs (negative:
+ *     unsupported sizes); workspace: sdt_clip_workspace_bytes(n_frames) bytes (negative: unsupported), written before it is read.
+ *   gather_poses: out (n_clips, num_frames, 3, 137) in the element type = src[starts[c] + i] with rows 0 and 1 (and row 2 if
+ *     scale_confidence) multiplied by scalar converted to the element type.
+ *   pcm_to_mono_f32: fmt 0 uint8 ((v - 128) / 128), 1 int16 (/ 2^15), 2 int32 (/ 2^31), 3 float32; interleaved frames
+ *     [first, n_samples) -> out, the channels (at most 8) averaged in float32.
+ *   resample_f32: y[j] = float32(sum_q taps[k0 + up*q] * x[t/up - q]), t = (j + n_pre_remove)*down, k0 = t % up, products and sums
+ *     in float64 in ascending q, x zero outside [0, n_in).  sdt_clip_resample_lds_bytes: the launch's LDS (negative: unsupported
+ *     filter length / ratio).
+ *   gather_audio: out (n_clips, l_max) = audio[a0[c] : a1[c]] clamped to the track, zero after its end; lengths[c] the slice length.
+ * No allocation; every pointer but scalar arguments is a device buffer; every index is checked against the sizes given.
+ */
+int64_t sdt_clip_workspace_bytes(int64_t n_frames);
+int sdt_clip_frame_flags(int elem_bytes, const void* src, const void* present, int64_t n_frames, int32_t* keep, double* dist, int32_t* bad,
+                         void* stream);
+int sdt_clip_scan(const int32_t* keep, const double* dist, int64_t n_frames, int32_t* prefix, double* dist_kept, void* stream);
+int sdt_clip_shoulder_means(const double* dist_kept, const int32_t* prefix, int64_t n_frames, int chunks, double* means, void* stream);
+int64_t sdt_clip_window_candidates(int64_t n_frames, int start_frame, int num_frames, int step);
+int sdt_clip_windows(const int32_t* prefix, int64_t n_frames, int start_frame, int num_frames, int step, void* workspace,
+                     int64_t workspace_bytes, int32_t* starts, int64_t starts_capacity, int32_t* n_clips, void* stream);
+int sdt_clip_gather_poses(int elem_bytes, const void* src, int64_t n_frames, const int32_t* starts, int64_t n_clips, int num_frames,
+                          double scalar, int scale_confidence, void* out, int64_t out_elems, void* stream);
+int sdt_clip_pcm_to_mono_f32(int fmt, const void* pcm, int64_t n_samples, int channels, int64_t first, float* out, int64_t out_elems,
+                             void* stream);
+int64_t sdt_clip_resample_lds_bytes(int n_taps, int up, int down);
+int sdt_clip_resample_f32(const float* x, int64_t n_in, const double* taps, int n_taps, int up, int down, int64_t n_pre_remove, float* y,
+                          int64_t n_out, void* stream);
+int sdt_clip_gather_audio(const float* audio, int64_t n_audio, const int64_t* a0, const int64_t* a1, int64_t n_clips, int64_t l_max,
+                          float* out, int64_t out_elems, int32_t* lengths, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -141,6 +141,17 @@ SIGNATURES = {
     "sdt_gif_quantise": [_p, _i64, _i, _i, _i, _i, _i, _p, _i64, _p, _i64, _p, _p, _i64, _p],
     "sdt_gif_measure": [_p, _i64, _i, _i, _i, _p, _i64, _p, _i64, _p, _p],
     "sdt_gif_pack": [_p, _i64, _i, _i, _i, _p, _i64, _p, _i64, _p, _p],
+    "sdt_clip_workspace_bytes": [_i64],  # (returns int64_t: restype set in load())
+    "sdt_clip_frame_flags": [_i, _p, _p, _i64, _p, _p, _p, _p],
+    "sdt_clip_scan": [_p, _p, _i64, _p, _p, _p],
+    "sdt_clip_shoulder_means": [_p, _p, _i64, _i, _p, _p],
+    "sdt_clip_window_candidates": [_i64, _i, _i, _i],  # (returns int64_t: restype set in load())
+    "sdt_clip_windows": [_p, _i64, _i, _i, _i, _p, _i64, _p, _i64, _p, _p],
+    "sdt_clip_gather_poses": [_i, _p, _i64, _p, _i64, _i, C.c_double, _i, _p, _i64, _p],
+    "sdt_clip_pcm_to_mono_f32": [_i, _p, _i64, _i, _i64, _p, _i64, _p],
+    "sdt_clip_resample_lds_bytes": [_i, _i, _i],  # (returns int64_t: restype set in load())
+    "sdt_clip_resample_f32": [_p, _i64, _p, _i, _i, _i, _i64, _p, _i64, _p],
+    "sdt_clip_gather_audio": [_p, _i64, _p, _p, _i64, _i64, _p, _i64, _p, _p],
 }
 F32, BF16 = 0, 1  # enum sdt_dtype
 
@@ -189,6 +200,9 @@ def load():
     lib.sdt_jpeg_workspace_bytes.restype = C.c_int64
     lib.sdt_jpeg_intervals.restype = C.c_int64
     lib.sdt_gif_workspace_bytes.restype = C.c_int64
+    lib.sdt_clip_workspace_bytes.restype = C.c_int64
+    lib.sdt_clip_window_candidates.restype = C.c_int64
+    lib.sdt_clip_resample_lds_bytes.restype = C.c_int64
     lib.sdt_conv_dw_group_plan_bytes.argtypes = [_i]
     lib.sdt_conv_dw_group_plan_bytes.restype = C.c_int64
     lib.sdt_conv_dw_workspace_bytes.argtypes = [_G]

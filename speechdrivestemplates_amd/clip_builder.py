@@ -1,0 +1,549 @@
+"""A custom speaker's clips, built on the GPU from per-frame keypoints and one wav per video (csrc/clip_builder.hip): the
+reference's data_preprocess/2_2_remove_outlier.py, 2_3_rescale_shoulder_width.py, 3_1_generate_clips.py and
+3_2_split_train_val_test.py without librosa, ffmpeg or tqdm, ending in the ``processed_137.csv`` and clip npz files that
+``GestureDataset`` and ``speaker_stats`` read.
+
+Inputs:  <root>/<speaker>/tmp/raw_pose_2d/<video>/<video>_<000123>.npy, (3, 137) float32 or float64 (one dtype per speaker)
+         <root>/<speaker>/audio_full/<video>.wav, PCM, any rate, covering the video from t = 0
+Outputs: <root>/<speaker>/clips/npz/<speaker>-<video>-<start>-<end>.npz (pose, imgs, audio), tmp/intermediate_csv/tmp_<video>.csv,
+         processed_137.csv (validation label ``dev``) and clips.csv (``val``, the reference's file)
+
+Contract: every arithmetic stage has a numpy model below (``model_*``), and the GPU result equals it bit for
+bit.  The models exist for the tests; ``build_clips`` has no CPU fallback.
+
+    python -m speechdrivestemplates_amd.clip_builder --root DIR --speaker NAME [--start-frame 80] [--frames 64]
+                                                     [--shoulder-chunks 1] [--no-write]
+"""
+import argparse
+import ctypes as C
+import os
+import time
+from concurrent.futures import ThreadPoolExecutor
+from math import gcd
+
+import numpy as np
+
+KP = 137
+KEEP_121 = [0] + list(range(2, 8)) + [15, 16] + list(range(25, 137))  # 2_2's pose137_to_pose121 (not the dataset's _KEEP_137)
+OLIVER_SHOULDER = 331.0850066245443  # 2_3:68
+FPS, SR, STEP, IDLE = 15, 16000, 5, 13  # 3_1:13-14, :167 (FPS // 3); 3_2:21
+TRAIN_RATIO = 0.8  # 3_2:17
+MAX_READ_THREADS = 16  # keypoint-file reading threads: a fixed cap, not os.cpu_count(), which counts every CPU of a shared host
+COLUMNS = ['dataset', 'start', 'end', 'interval_id', 'pose_fn', 'audio_fn', 'video_fn', 'speaker']  # 3_1:140-141
+_PCM_FMT = {'uint8': 0, 'int16': 1, 'int32': 2, 'float32': 3}
+
+
+# ---------------------------------------------------------------------------------------------------------- planning (names only)
+
+def plan_clips(root_dir, speaker):
+    """-> [{'video', 'dir', 'frames': {index: path}, 'n_frames': highest index + 1, 'wav'}], videos sorted by name; lists
+    directories and opens no file"""
+    base = os.path.join(root_dir, speaker)
+    pose_root = os.path.join(base, 'tmp', 'raw_pose_2d')
+    if not os.path.isdir(pose_root):
+        raise FileNotFoundError('No keypoint directory: %s' % pose_root)
+    plan = []
+    for video in sorted(os.listdir(pose_root)):
+        d = os.path.join(pose_root, video)
+        if not os.path.isdir(d):
+            continue
+        frames = {}
+        for fn in sorted(os.listdir(d)):
+            stem, ext = os.path.splitext(fn)
+            head, _, num = stem.rpartition('_')
+            if ext != '.npy' or head != video or not num.isdigit():
+                raise ValueError('%s: not a keypoint file of video %s (<video>_<frame index>.npy expected)' % (os.path.join(d, fn), video))
+            frames[int(num)] = os.path.join(d, fn)
+        plan.append({'video': video, 'dir': d, 'frames': frames, 'n_frames': (max(frames) + 1) if frames else 0,
+                     'wav': os.path.join(base, 'audio_full', video + '.wav')})
+    if not plan:
+        raise ValueError('%s holds no video directory' % pose_root)
+    return plan
+
+
+# ------------------------------------------------------------------------------------------------------------------ contract models
+
+def model_frame_flags(src, present):
+    """src (n, 3, 137), present (n,) bool -> keep (n,) bool, dist (n,) float64 (0 for dropped frames).  2_2:15-23, 2_3:23-25."""
+    p = src[:, :2, :][:, :, KEEP_121]
+    outlier = ((p[:, 0] <= 3) & (p[:, 1] <= 3)).any(axis=1)
+    keep = np.asarray(present, bool) & ~outlier
+    x = src[:, :2, :].astype(np.float64)
+    dx, dy = x[:, 0, 2] - x[:, 0, 5], x[:, 1, 2] - x[:, 1, 5]
+    with np.errstate(invalid='ignore'):
+        dist = np.sqrt(dx * dx + dy * dy)
+    return keep, np.where(keep, dist, 0.0)
+
+
+def model_shoulder_means(dist_kept, chunks):
+    """the kept frames' distances in file-name order -> (per-chunk running means (chunks,), frames dropped by the chunking).
+    2_3:28-43 and :50-52, in float64, every operation rounded on its own"""
+    n = len(dist_kept)
+    stride = n // chunks
+    means = np.zeros(chunks, np.float64)
+    for c in range(chunks):
+        avg, num = np.float64(0.0), 0
+        for d in dist_kept[c * stride:(c + 1) * stride]:
+            weight = num / (num + 1)
+            avg = avg * weight + (1 - weight) * np.float64(d)
+            num += 1
+        means[c] = avg
+    return means, n - stride * chunks
+
+
+def model_scalar(means):
+    """2_3:59, :71 (oliver_scalar = 1.0)"""
+    return float(OLIVER_SHOULDER * 1.0 / np.average(np.asarray(means, np.float64), axis=0))
+
+
+def scales_confidence(shoulder_chunks, scale_confidence=None):
+    """the reference multiplies the whole (3, 137) array with -np 1 (2_3:92-95) and rows 0 and 1 only with -np > 1 (:75-79)"""
+    return (shoulder_chunks == 1) if scale_confidence is None else bool(scale_confidence)
+
+
+def model_scale(frames, scalar, scale_conf):
+    """frames (..., 3, 137) in the file's dtype times the scalar as a python float: the product is formed in that dtype"""
+    out = frames.copy()
+    if scale_conf:
+        return out * float(scalar)
+    out[..., :2, :] = out[..., :2, :] * float(scalar)
+    return out
+
+
+def model_clip_starts(keep, start_frame, num_frames):
+    """3_1:168-215: a window is a clip iff every one of its frames has a file"""
+    n = len(keep)
+    pre = np.concatenate([[0], np.cumsum(np.asarray(keep, np.int64))])
+    return [s for s in range(start_frame, n - num_frames, STEP) if pre[s + num_frames] - pre[s] == num_frames]
+
+
+def frame_idx_to_time(frame_idx):
+    """3_1:90-97"""
+    all_seconds = frame_idx / float(FPS)
+    hour = int(all_seconds // 3600)
+    minute = int((all_seconds % 3600) // 60)
+    seconds = (all_seconds % 3600) % 60
+    return f"{hour:02d}:{minute:02d}:{seconds:09.6f}"
+
+
+def time_to_us(text):
+    """the microseconds pandas.to_timedelta reads from frame_idx_to_time's string"""
+    h, m, s = text.split(':')
+    whole, frac = s.split('.')
+    return (int(h) * 3600 + int(m) * 60 + int(whole)) * 1000000 + int(frac)
+
+
+def audio_offsets(frame_idx, start_frame, num_frames):
+    """3_1:172-175: (int(audio_start), int(audio_end)) in 16 kHz samples from the cut at start_frame"""
+    t0 = time_to_us(frame_idx_to_time(start_frame))
+    a0 = (time_to_us(frame_idx_to_time(frame_idx)) - t0) / 1e6 * SR
+    a1 = (time_to_us(frame_idx_to_time(frame_idx + num_frames)) - t0) / 1e6 * SR
+    return int(a0), int(a1)
+
+
+def source_cut(start_frame, sr_in):
+    """the source sample the track is cut at: int(start_seconds * sr_in), start_seconds rounded to the microsecond"""
+    return int(time_to_us(frame_idx_to_time(start_frame)) / 1e6 * sr_in)
+
+
+def model_pcm_to_mono(a):
+    """wavfile.read's array -> float32 mono, gesture_dataset._demo_item's conversion"""
+    if a.dtype.kind == 'i':
+        a = a.astype(np.float32) / float(2 ** (8 * a.dtype.itemsize - 1))
+    elif a.dtype.kind == 'u':
+        a = (a.astype(np.float32) - 128.0) / 128.0
+    else:
+        a = a.astype(np.float32)
+    if a.ndim == 2:
+        a = a.mean(axis=1)
+    return a
+
+
+def design_taps(sr_in, sr_out=SR):
+    """-> (up, down, taps float64 with the leading zero pad, n_pre_remove): scipy.signal.resample_poly's default filter
+    (firwin(2*10*max(up, down) + 1, 1/max(up, down), window=('kaiser', 5.0)) * up) and its centring"""
+    from scipy.signal import firwin
+    g = gcd(int(sr_in), int(sr_out))
+    up, down = int(sr_out) // g, int(sr_in) // g
+    max_rate = max(up, down)
+    half_len = 10 * max_rate
+    h = firwin(2 * half_len + 1, 1. / max_rate, window=('kaiser', 5.0)).astype(np.float64)
+    h *= up
+    n_pre_pad = down - half_len % down
+    return up, down, np.concatenate([np.zeros(n_pre_pad), h]), (half_len + n_pre_pad) // down
+
+
+def resampled_length(n_in, up, down):
+    n = n_in * up
+    return n // down + bool(n % down)
+
+
+def model_resample(x, sr_in, sr_out=SR, dtype=np.float32):
+    """polyphase FIR of float32 (or float64) samples: y[j] = sum_q taps[k0 + up*q] * x[t//up - q], t = (j + n_pre_remove)*down,
+    k0 = t % up, accumulated in float64 in ascending q with x zero outside the track, rounded once to ``dtype``"""
+    x = np.asarray(x)
+    if int(sr_in) == int(sr_out):
+        return x.astype(dtype)
+    up, down, taps, n_pre = design_taps(sr_in, sr_out)
+    n_in = len(x)
+    n_out = resampled_length(n_in, up, down)
+    t = (np.arange(n_out, dtype=np.int64) + n_pre) * down
+    k0, ib = t % up, t // up
+    x64 = x.astype(np.float64)
+    acc = np.zeros(n_out, np.float64)
+    for q in range((len(taps) + up - 1) // up):
+        k, i = k0 + up * q, ib - q
+        ok = (k < len(taps)) & (i >= 0) & (i < n_in)
+        prod = taps[np.where(ok, k, 0)] * x64[np.where(ok, i, 0)]
+        acc = np.where(ok, acc + prod, acc)
+    return acc.astype(dtype)
+
+
+def split_labels(n, val_label='dev'):
+    """3_2:31-43: the first int(0.8 n) clips train, the next 13 idle, the rest validation"""
+    n_train = int(n * TRAIN_RATIO)
+    n_idle = min(IDLE, n - n_train)
+    return ['train'] * n_train + ['idle'] * n_idle + [val_label] * (n - n_train - n_idle)
+
+
+# ----------------------------------------------------------------------------------------------------------------------- host I/O
+
+def _read_frames(video, dtype, pool):
+    """-> (src (n, 3, 137) pinned torch tensor, present (n,) uint8 numpy); missing frames stay zero"""
+    import torch
+    n = video['n_frames']
+    src = torch.zeros((n, 3, KP), dtype=dtype).pin_memory()
+    dst = src.numpy()
+    present = np.zeros(n, np.uint8)
+
+    def one(item):
+        idx, path = item
+        a = np.load(path)
+        if a.shape != (3, KP):
+            raise ValueError('%s: shape %s, expected (3, 137)' % (path, a.shape))
+        if a.dtype != dst.dtype:
+            raise ValueError('%s: dtype %s, but the first keypoint file of the speaker is %s (one dtype per speaker)' % (path, a.dtype, dst.dtype))
+        dst[idx] = a
+        present[idx] = 1
+    for f in [pool.submit(one, it) for it in video['frames'].items()]:
+        f.result()
+    return src, present
+
+
+def _read_wav(path):
+    from scipy.io import wavfile
+    if not os.path.exists(path):
+        raise FileNotFoundError('No audio track: %s' % path)
+    sr, a = wavfile.read(path)
+    if str(a.dtype) not in _PCM_FMT:
+        raise ValueError('%s: %s samples (uint8, int16, int32 or float32 PCM expected)' % (path, a.dtype))
+    if a.ndim == 2 and a.shape[1] > 8:
+        raise ValueError('%s: %d channels (at most 8)' % (path, a.shape[1]))
+    return int(sr), np.ascontiguousarray(a)
+
+
+def frame_image_paths(root_dir, speaker, video, start, num_frames):
+    """3_1:113-118, :187-189: the frame paths, from names alone"""
+    d = os.path.join(root_dir, speaker, 'frames', video)
+    return np.array([os.path.join(d, video + f"_{str(start + i).zfill(6)}.jpg") for i in range(num_frames)])
+
+
+def clip_relpath(speaker, video, start, num_frames):
+    return os.path.join('clips', 'npz', '%s-%s-%s-%s.npz' % (speaker, video, start, start + num_frames))
+
+
+def video_table(speaker, video, starts, num_frames):
+    """the rows 3_1 writes to tmp_<video>.csv; pose_fn relative to <root>/<speaker> (the form speaker_stats and GestureDataset join)"""
+    import pandas as pd
+    rows = {c: [] for c in COLUMNS}
+    for s in starts:
+        rows['dataset'].append('train')
+        rows['start'].append(int(s))
+        rows['end'].append(int(s) + num_frames)
+        rows['interval_id'].append(video)
+        rows['pose_fn'].append(clip_relpath(speaker, video, int(s), num_frames))
+        rows['audio_fn'].append(os.path.join('audio_full', video + '.wav'))
+        rows['video_fn'].append(video)
+        rows['speaker'].append(speaker)
+    return pd.DataFrame(rows, columns=COLUMNS)
+
+
+def split_table(tables, val_label='dev'):
+    """3_2:28-47 over the per-video tables (videos sorted by name): all train rows, then all idle rows, then all validation rows"""
+    import pandas as pd
+    parts = [[], [], []]
+    for df in tables:
+        df = df.copy()
+        df['dataset'] = split_labels(len(df), val_label)
+        for i, lab in enumerate(('train', 'idle', val_label)):
+            parts[i].append(df[df['dataset'] == lab])
+    return pd.concat([pd.concat(p) for p in parts])
+
+
+def write_split_csv(root_dir, speaker, tables):
+    """processed_137.csv (label ``dev``: what GestureDataset and speaker_stats select) and clips.csv (``val``: the reference's file)"""
+    base = os.path.join(root_dir, speaker)
+    out = {}
+    for name, label in (('processed_137.csv', 'dev'), ('clips.csv', 'val')):
+        out[name] = os.path.join(base, name)
+        split_table(tables, label).to_csv(out[name], index=False)
+    return out
+
+
+# ------------------------------------------------------------------------------------------------------------------------ the GPU
+
+def _p(t):
+    return C.c_void_p(t.data_ptr() if t.numel() else None)
+
+
+class _Timer:
+    """HIP-event time per stage, summed after the video's last kernel"""
+
+    def __init__(self, stream):
+        import torch
+        self.torch, self.stream, self.spans = torch, stream, []
+
+    def run(self, stage, fn):
+        a, b = self.torch.cuda.Event(enable_timing=True), self.torch.cuda.Event(enable_timing=True)
+        a.record(self.stream)
+        fn()
+        b.record(self.stream)
+        self.spans.append((stage, a, b))
+
+    def totals(self):
+        out = {}
+        for stage, a, b in self.spans:
+            out[stage] = out.get(stage, 0.0) + a.elapsed_time(b)
+        return out
+
+
+def device_frame_stages(src, present, start_frame, num_frames, shoulder_chunks, timer=None):
+    """the per-video pose stages up to the clip starts.  src (n, 3, 137) and present (n,) uint8 on the device ->
+    dict(keep, dist, bad, prefix, dist_kept, means, starts (capacity), n_clips (device int32))"""
+    import torch
+    from . import _lib
+    lib = _lib.load()
+    dev, n = src.device, src.shape[0]
+    raw = torch.cuda.current_stream(dev).cuda_stream
+    esize = src.element_size()
+    run = timer.run if timer is not None else (lambda stage, fn: fn())
+    ws_bytes = lib.sdt_clip_workspace_bytes(n)
+    n_cand = lib.sdt_clip_window_candidates(n, start_frame, num_frames, STEP)
+    if ws_bytes < 0 or n_cand < 0:
+        raise ValueError('unsupported frame count / start / window (%d, %d, %d)' % (n, start_frame, num_frames))
+    o = {'keep': torch.empty(n, dtype=torch.int32, device=dev), 'dist': torch.empty(n, dtype=torch.float64, device=dev),
+         'bad': torch.empty(n, dtype=torch.int32, device=dev), 'prefix': torch.empty(n + 1, dtype=torch.int32, device=dev),
+         'dist_kept': torch.zeros(n, dtype=torch.float64, device=dev), 'means': torch.empty(shoulder_chunks, dtype=torch.float64, device=dev),
+         'starts': torch.empty(max(n_cand, 1), dtype=torch.int32, device=dev), 'n_clips': torch.empty(1, dtype=torch.int32, device=dev)}
+    ws = torch.empty(max(ws_bytes, 4), dtype=torch.uint8, device=dev)
+    run('flags', lambda: _lib.check(lib.sdt_clip_frame_flags(esize, _p(src), _p(present), n, _p(o['keep']), _p(o['dist']), _p(o['bad']), raw)))
+    run('scan', lambda: _lib.check(lib.sdt_clip_scan(_p(o['keep']), _p(o['dist']), n, _p(o['prefix']), _p(o['dist_kept']), raw)))
+    run('shoulder', lambda: _lib.check(lib.sdt_clip_shoulder_means(_p(o['dist_kept']), _p(o['prefix']), n, shoulder_chunks, _p(o['means']), raw)))
+    run('windows', lambda: _lib.check(lib.sdt_clip_windows(_p(o['prefix']), n, start_frame, num_frames, STEP, _p(ws), ws.numel(),
+                                                          _p(o['starts']), o['starts'].numel(), _p(o['n_clips']), raw)))
+    return o
+
+
+def device_gather_poses(src, starts, n_clips, num_frames, scalar, scale_conf):
+    """-> (n_clips, num_frames, 3, 137) in src's dtype"""
+    import torch
+    from . import _lib
+    lib = _lib.load()
+    out = torch.empty((n_clips, num_frames, 3, KP), dtype=src.dtype, device=src.device)
+    if n_clips:
+        _lib.check(lib.sdt_clip_gather_poses(src.element_size(), _p(src), src.shape[0], _p(starts), n_clips, num_frames, float(scalar),
+                                             int(bool(scale_conf)), _p(out), out.numel(), torch.cuda.current_stream(src.device).cuda_stream))
+    return out
+
+
+def upload_pcm(pcm, device='cuda'):
+    import torch
+    return torch.from_numpy(np.ascontiguousarray(pcm).view(np.uint8).reshape(-1)).to(device)
+
+
+def device_pcm_to_mono(pcm, first=0, device='cuda', raw=None):
+    """wavfile.read's array (host; ``raw``: its bytes already on the device) -> float32 mono on the device, from source sample
+    ``first`` on"""
+    import torch
+    from . import _lib
+    lib = _lib.load()
+    n = pcm.shape[0]
+    ch = pcm.shape[1] if pcm.ndim == 2 else 1
+    if first >= n:
+        return torch.empty(0, dtype=torch.float32, device=device)
+    if raw is None:
+        raw = upload_pcm(pcm, device)
+    out = torch.empty(n - first, dtype=torch.float32, device=device)
+    _lib.check(lib.sdt_clip_pcm_to_mono_f32(_PCM_FMT[str(pcm.dtype)], _p(raw), n, ch, first, _p(out), out.numel(),
+                                            torch.cuda.current_stream(out.device).cuda_stream))
+    return out
+
+
+def device_resample(x, sr_in, sr_out=SR):
+    """float32 mono on the device at sr_in -> at sr_out (the same tensor when the rates are equal)"""
+    import torch
+    from . import _lib
+    lib = _lib.load()
+    if int(sr_in) == int(sr_out) or x.numel() == 0:
+        return x
+    up, down, taps, n_pre = design_taps(sr_in, sr_out)
+    if lib.sdt_clip_resample_lds_bytes(len(taps), up, down) < 0:
+        raise ValueError('unsupported sample rate %d (ratio %d/%d, %d taps)' % (sr_in, up, down, len(taps)))
+    n_out = resampled_length(x.numel(), up, down)
+    y = torch.empty(n_out, dtype=torch.float32, device=x.device)
+    t = torch.from_numpy(taps).to(x.device)
+    _lib.check(lib.sdt_clip_resample_f32(_p(x), x.numel(), _p(t), len(taps), up, down, n_pre, _p(y), n_out,
+                                         torch.cuda.current_stream(x.device).cuda_stream))
+    return y
+
+
+def device_gather_audio(audio, a0, a1):
+    """audio (float32, device), a0 / a1 sequences of slice bounds -> ((n_clips, L_max) zero-padded, lengths int32)"""
+    import torch
+    from . import _lib
+    lib = _lib.load()
+    dev, n = audio.device, len(a0)
+    l_max = max(1, max((int(b) - int(a) for a, b in zip(a0, a1)), default=1))
+    out = torch.zeros((n, l_max), dtype=torch.float32, device=dev)
+    lengths = torch.zeros(n, dtype=torch.int32, device=dev)
+    if n and audio.numel():
+        t0 = torch.tensor(list(a0), dtype=torch.int64).to(dev)
+        t1 = torch.tensor(list(a1), dtype=torch.int64).to(dev)
+        _lib.check(lib.sdt_clip_gather_audio(_p(audio), audio.numel(), _p(t0), _p(t1), n, l_max, _p(out), out.numel(), _p(lengths),
+                                             torch.cuda.current_stream(dev).cuda_stream))
+    return out, lengths
+
+
+def build_clips(root_dir, speaker, start_frame=80, num_frames=64, shoulder_chunks=1, scale_confidence=None, write=True, device='cuda'):
+    """-> {'videos': {name: summary}, 'table' (processed_137 order), 'timing'} and, with write=False, 'poses' (n_clips, num_frames, 3, 137),
+    'audio' (n_clips, L_max), 'audio_lengths' (n_clips,) on the device in per-video, ascending-start order, with 'order' giving
+    each table row's position in them"""
+    import torch
+    from . import _lib
+    dev = torch.device(device)
+    if dev.type != 'cuda':
+        raise RuntimeError('clips are built on the GPU (csrc/clip_builder.hip); there is no CPU fallback')
+    _lib.load()
+    if int(shoulder_chunks) < 1 or int(num_frames) < 1 or int(start_frame) < 0:
+        raise ValueError('shoulder_chunks and num_frames must be at least 1, start_frame at least 0')
+    plan = plan_clips(root_dir, speaker)
+    first = next((p for v in plan for p in v['frames'].values()), None)
+    if first is None:
+        raise ValueError('no keypoint file under %s' % os.path.join(root_dir, speaker, 'tmp', 'raw_pose_2d'))
+    np_dtype = np.load(first).dtype
+    if np_dtype not in (np.float32, np.float64):
+        raise ValueError('%s: dtype %s (float32 or float64 expected)' % (first, np_dtype))
+    dtype = torch.float32 if np_dtype == np.float32 else torch.float64
+    scale_conf = scales_confidence(shoulder_chunks, scale_confidence)
+    base = os.path.join(root_dir, speaker)
+    if write:
+        os.makedirs(os.path.join(base, 'clips', 'npz'), exist_ok=True)
+        os.makedirs(os.path.join(base, 'tmp', 'intermediate_csv'), exist_ok=True)
+    st = torch.cuda.current_stream(dev)
+    pool = ThreadPoolExecutor(max_workers=MAX_READ_THREADS)
+    summary, tables, all_poses, all_audio, all_len = {}, [], [], [], []
+    t_all = time.perf_counter()
+    try:
+        for video in plan:
+            name, n = video['video'], video['n_frames']
+            if not video['frames']:
+                raise ValueError('%s: no kept frame (the directory is empty)' % video['dir'])
+            t0 = time.perf_counter()
+            src_host, present = _read_frames(video, dtype, pool)
+            sr_in, pcm = _read_wav(video['wav'])
+            t_read = time.perf_counter() - t0
+            timer = _Timer(st)
+            src = src_host.to(dev, non_blocking=True)
+            o = device_frame_stages(src, torch.from_numpy(present).to(dev), start_frame, num_frames, shoulder_chunks, timer)
+            n_clips = int(o['n_clips'].item())  # (synchronises)
+            bad = o['bad'].cpu().numpy()
+            if bad.any():
+                raise ValueError('%s: non-finite keypoint coordinates' % video['frames'][int(np.flatnonzero(bad)[0])])
+            n_kept = int(o['prefix'][n].item())
+            if n_kept == 0:
+                raise ValueError('%s: no kept frame (every frame is an outlier)' % video['dir'])
+            means = o['means'].cpu().numpy()
+            mean = np.average(means, axis=0)
+            if not mean > 0:
+                raise ValueError('%s: mean shoulder distance %r over %d kept frames in %d chunk(s); cannot rescale'
+                                 % (video['dir'], float(mean), n_kept, shoulder_chunks))
+            scalar = float(OLIVER_SHOULDER * 1.0 / mean)
+            starts = o['starts'][:n_clips].cpu().numpy().astype(np.int64)
+            holder = {}
+            timer.run('gather_poses', lambda: holder.__setitem__('poses', device_gather_poses(src, o['starts'], n_clips, num_frames, scalar, scale_conf)))
+            cut = source_cut(start_frame, sr_in)
+            raw_pcm = upload_pcm(pcm, dev)
+            timer.run('pcm', lambda: holder.__setitem__('mono', device_pcm_to_mono(pcm, cut, dev, raw_pcm)))
+            timer.run('resample', lambda: holder.__setitem__('audio', device_resample(holder['mono'], sr_in)))
+            offs = [audio_offsets(int(s), start_frame, num_frames) for s in starts]
+            timer.run('gather_audio', lambda: holder.__setitem__('clips', device_gather_audio(holder['audio'], [a for a, _ in offs], [b for _, b in offs])))
+            torch.cuda.synchronize(dev)
+            poses, (audio, lengths) = holder['poses'], holder['clips']
+            table = video_table(speaker, name, starts, num_frames)
+            tables.append(table)
+            t_write = 0.0
+            if write:
+                t0 = time.perf_counter()
+                ph, ah, lh = poses.cpu().numpy(), audio.cpu().numpy(), lengths.cpu().numpy()
+
+                def save(i):
+                    np.savez(os.path.join(base, table['pose_fn'].iloc[i]), pose=ph[i],
+                             imgs=frame_image_paths(root_dir, speaker, name, int(starts[i]), num_frames), audio=ah[i, :lh[i]])
+                for f in [pool.submit(save, i) for i in range(n_clips)]:
+                    f.result()
+                table.to_csv(os.path.join(base, 'tmp', 'intermediate_csv', 'tmp_%s.csv' % name), index=False)
+                t_write = time.perf_counter() - t0
+            else:
+                all_poses.append(poses)
+                all_audio.append(audio)
+                all_len.append(lengths)
+            labels = split_labels(n_clips)
+            n_present = int(present.sum())
+            summary[name] = {'frames': n, 'missing': n - n_present, 'kept': n_kept, 'dropped': n - n_kept, 'outliers': n_present - n_kept,
+                             'shoulder_dropped': n_kept - (n_kept // shoulder_chunks) * shoulder_chunks, 'scalar': scalar,
+                             'scale_confidence': scale_conf, 'sample_rate': sr_in, 'audio_samples': int(holder['audio'].numel()),
+                             'clips': {lab: labels.count(lab) for lab in ('train', 'idle', 'dev')},
+                             'timing': {'kernel_ms': timer.totals(), 'read_s': t_read, 'write_s': t_write}}
+    finally:
+        pool.shutdown()
+    import pandas as pd
+    offsets = np.cumsum([0] + [len(t) for t in tables])
+    tagged = [t.assign(_pos=np.arange(offsets[i], offsets[i + 1])) for i, t in enumerate(tables)]
+    full = split_table(tagged, 'dev')
+    out = {'videos': summary, 'table': full[COLUMNS].reset_index(drop=True), 'order': full['_pos'].to_numpy().astype(np.int64),
+           'dtype': str(np_dtype), 'timing': {'total_s': time.perf_counter() - t_all}}
+    if write:
+        out['files'] = write_split_csv(root_dir, speaker, tables)
+    else:
+        l_max = max([a.shape[1] for a in all_audio] + [1])
+        out['poses'] = torch.cat(all_poses) if all_poses else torch.empty((0, num_frames, 3, KP), dtype=dtype, device=dev)
+        out['audio'] = torch.cat([torch.nn.functional.pad(a, (0, l_max - a.shape[1])) for a in all_audio])
+        out['audio_lengths'] = torch.cat(all_len)
+    assert isinstance(out['table'], pd.DataFrame)
+    return out
+
+
+def main(argv=None):
+    ap = argparse.ArgumentParser(description="a speaker's clips on the GPU from per-frame keypoints and one wav per video (the reference's "
+                                             "2_2, 2_3, 3_1 and 3_2) -> clips/npz, processed_137.csv, clips.csv")
+    ap.add_argument('--root', required=True, help='dataset root (DATASET.ROOT_DIR)')
+    ap.add_argument('--speaker', required=True)
+    ap.add_argument('--start-frame', type=int, default=80, help="frames before it are dropped (3_1's -fi)")
+    ap.add_argument('--frames', type=int, default=64, help='frames per clip (DATASET.NUM_FRAMES)')
+    ap.add_argument('--shoulder-chunks', type=int, default=1, help="chunks of the shoulder-distance mean (2_3's -np)")
+    ap.add_argument('--no-write', action='store_true', help='build on the device and print the summary only')
+    a = ap.parse_args(argv)
+    res = build_clips(a.root, a.speaker, start_frame=a.start_frame, num_frames=a.frames, shoulder_chunks=a.shoulder_chunks, write=not a.no_write)
+    for name, s in res['videos'].items():
+        k = s['timing']
+        print('video %s: %d frames, %d kept, %d dropped (%d missing), %d shoulder frames dropped by chunking, scalar %.9g, clips %d train / '
+              '%d idle / %d dev (%.2f s reading, kernels %.3f ms, %.2f s writing)'
+              % (name, s['frames'], s['kept'], s['dropped'], s['missing'], s['shoulder_dropped'], s['scalar'], s['clips']['train'],
+                 s['clips']['idle'], s['clips']['dev'], k['read_s'], sum(k['kernel_ms'].values()), k['write_s']))
+    print('speaker %s: %d clips in %.2f s%s' % (a.speaker, len(res['table']), res['timing']['total_s'],
+                                                '' if a.no_write else ' -> ' + res['files']['processed_137.csv']))
+    return 0
+
+
+if __name__ == '__main__':
+    raise SystemExit(main())

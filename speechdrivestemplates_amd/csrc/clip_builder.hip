@@ -1,0 +1,413 @@
+// Clip preparation (data_preprocess/2_2_remove_outlier.py, 2_3_rescale_shoulder_width.py, 3_1_generate_clips.py of the reference)
+// from one video's per-frame keypoints (N, 3, 137) and its PCM track.  Stages, one kernel each:
+//   frame flags      one wave per group of frames: the 2_2 outlier test over the 121 kept keypoints as a wave ballot, the shoulder
+//                    distance of 2_3 in float64, a non-finite flag
+//   scan             exclusive prefix sum of the keep flags (integers) and the kept frames' distances packed in frame order
+//   shoulder means   2_3's serial recurrence avg = avg*(num/(num+1)) + (1 - num/(num+1))*d, one lane per chunk
+//   window measure / pack   a window of F frames is a clip iff the prefix sum says all F are kept; the starts are compacted in
+//                    ascending order in two passes (count per block, then write at the block's offset)
+//   pose gather      (n_clips, F, 3, 137) = the window's frames times the scalar, the product formed in the element type
+//   pcm              integer / float PCM -> float32, channels averaged
+//   resample         polyphase FIR with float64 taps, float64 accumulation in ascending tap order, one rounding to float32
+//   audio gather     per-clip slices with a length table
+// Every floating-point operation is rounded on its own (contraction is off for the whole file) and no floating-point value is
+// accumulated with atomics, so every output is a fixed function of the inputs.  Contract and numbers: DESIGN.md section 16.
+#include "common.h"
+
+#pragma clang fp contract(off)
+
+namespace {
+
+constexpr int kKp = 137, kFrameElems = 3 * kKp, kThreads = 256, kFramesPerWave = 4;
+constexpr int kResTile = 64;                 // outputs per tile of the resampler: one per lane of its single wave
+constexpr int kResTilesPerBlock = 8;         // tiles a block walks when every phase's taps are resident (up <= kResTile)
+constexpr int64_t kResMaxLds = 60 * 1024;
+
+// 2_2's pose137_to_pose121: 0, 2..7, 15, 16, 25..136
+__device__ __forceinline__ bool kept121(int k) { return k == 0 || (k >= 2 && k <= 7) || k == 15 || k == 16 || k >= 25; }
+
+template <typename T>
+__global__ void __launch_bounds__(kThreads) clip_frame_flags_kernel(const T* __restrict__ src, const uint8_t* __restrict__ present,
+                                                                    int64_t n, int32_t* __restrict__ keep, double* __restrict__ dist,
+                                                                    int32_t* __restrict__ bad) {
+    const int64_t wave = ((int64_t)blockIdx.x * kThreads + threadIdx.x) / 64;
+    const int lane = threadIdx.x & 63;
+    for (int g = 0; g < kFramesPerWave; ++g) {
+        const int64_t f = wave * kFramesPerWave + g;
+        if (f >= n) break;  // uniform over the wave
+        const T* p = src + f * kFrameElems;
+        const bool pres = present[f] != 0;
+        bool outlier = false, nonfinite = false;
+        if (pres) {
+            for (int k = lane; k < kKp; k += 64) {
+                const T x = p[k], y = p[kKp + k];
+                nonfinite |= !(isfinite(x) && isfinite(y));
+                if (kept121(k)) outlier |= (x <= T(3) && y <= T(3));
+            }
+        }
+        const bool any_out = __ballot(outlier) != 0, any_nf = __ballot(nonfinite) != 0;
+        if (lane == 0) {
+            const bool kp = pres && !any_out;
+            double d = 0.0;
+            if (kp) {
+                const double dx = (double)p[2] - (double)p[5], dy = (double)p[kKp + 2] - (double)p[kKp + 5];
+                d = __dsqrt_rn(dx * dx + dy * dy);
+            }
+            keep[f] = kp ? 1 : 0;
+            bad[f] = (kp && any_nf) ? 1 : 0;
+            dist[f] = d;
+        }
+    }
+}
+
+// one workgroup walks the frames in tiles of kThreads: prefix[f] = kept frames before f, prefix[n] = all of them
+__global__ void __launch_bounds__(kThreads) clip_scan_kernel(const int32_t* __restrict__ keep, const double* __restrict__ dist, int64_t n,
+                                                             int32_t* __restrict__ prefix, double* __restrict__ dist_kept) {
+    __shared__ int wsum[kThreads / 64];
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    int carry = 0;
+    for (int64_t base = 0; base < n; base += kThreads) {
+        const int64_t f = base + threadIdx.x;
+        const bool v = f < n && keep[f] != 0;
+        const unsigned long long mask = __ballot(v);
+        const int excl = __popcll(mask & ((1ull << lane) - 1ull));
+        if (lane == 0) wsum[w] = __popcll(mask);
+        __syncthreads();
+        int woff = 0, tot = 0;
+#pragma unroll
+        for (int i = 0; i < kThreads / 64; ++i) {
+            if (i < w) woff += wsum[i];
+            tot += wsum[i];
+        }
+        const int at = carry + woff + excl;
+        if (f < n) {
+            prefix[f] = at;
+            if (v) dist_kept[at] = dist[f];
+        }
+        carry += tot;
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) prefix[n] = carry;
+}
+
+// lane c: the running mean of kept frames [c*stride, (c+1)*stride), stride = kept // chunks (2_3:28-43, :50-52)
+__global__ void __launch_bounds__(64) clip_shoulder_means_kernel(const double* __restrict__ dist_kept, const int32_t* __restrict__ prefix,
+                                                                 int64_t n, int chunks, double* __restrict__ means) {
+    const int c = blockIdx.x * 64 + threadIdx.x;
+    if (c >= chunks) return;
+    const int64_t stride = (int64_t)prefix[n] / chunks;
+    const double* d = dist_kept + (int64_t)c * stride;
+    double avg = 0.0, num = 0.0;
+    for (int64_t j = 0; j < stride; ++j) {
+        const double weight = num / (num + 1.0);
+        avg = avg * weight + (1.0 - weight) * d[j];
+        num = num + 1.0;
+    }
+    means[c] = avg;
+}
+
+__device__ __forceinline__ bool window_valid(const int32_t* prefix, int64_t i, int64_t n_cand, int start, int step, int F, int* s_out) {
+    if (i >= n_cand) return false;
+    const int s = start + (int)i * step;
+    *s_out = s;
+    return prefix[s + F] - prefix[s] == F;
+}
+
+// measure (kPack false): block_counts[b] = valid windows among candidates [b*kThreads, (b+1)*kThreads)
+// pack (kPack true): the valid starts written in ascending order at the block's offset; the last block writes the total
+template <bool kPack>
+__global__ void __launch_bounds__(kThreads) clip_windows_kernel(const int32_t* __restrict__ prefix, int64_t n_cand, int start, int step, int F,
+                                                                int32_t* __restrict__ block_counts, int32_t* __restrict__ starts,
+                                                                int32_t* __restrict__ n_clips) {
+    __shared__ int wsum[kThreads / 64];
+    __shared__ int s_off;
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    int s = 0;
+    const bool v = window_valid(prefix, (int64_t)blockIdx.x * kThreads + threadIdx.x, n_cand, start, step, F, &s);
+    const unsigned long long mask = __ballot(v);
+    if (lane == 0) wsum[w] = __popcll(mask);
+    if (kPack && threadIdx.x == 0) {
+        int off = 0;
+        for (unsigned b = 0; b < blockIdx.x; ++b) off += block_counts[b];
+        s_off = off;
+    }
+    __syncthreads();
+    int woff = 0, tot = 0;
+#pragma unroll
+    for (int i = 0; i < kThreads / 64; ++i) {
+        if (i < w) woff += wsum[i];
+        tot += wsum[i];
+    }
+    if (!kPack) {
+        if (threadIdx.x == 0) block_counts[blockIdx.x] = tot;
+        return;
+    }
+    if (v) starts[s_off + woff + __popcll(mask & ((1ull << lane) - 1ull))] = s;
+    if (blockIdx.x == gridDim.x - 1 && threadIdx.x == 0) *n_clips = s_off + tot;
+}
+
+template <typename T>
+__global__ void __launch_bounds__(kThreads) clip_gather_poses_kernel(const T* __restrict__ src, int64_t n, const int32_t* __restrict__ starts,
+                                                                     int64_t total, int F, double scalar, int scale_conf, T* __restrict__ out) {
+    const int64_t idx = (int64_t)blockIdx.x * kThreads + threadIdx.x;
+    if (idx >= total) return;
+    const int64_t per_clip = (int64_t)F * kFrameElems;
+    const int64_t c = idx / per_clip, rem = idx % per_clip;
+    const int i = (int)(rem / kFrameElems), e = (int)(rem % kFrameElems);
+    const int64_t f = (int64_t)starts[c] + i;
+    if (f < 0 || f >= n) return;  // (starts come from the pack pass, which only emits windows inside the video)
+    T v = src[f * kFrameElems + e];
+    if (e < 2 * kKp || scale_conf) v = v * (T)scalar;  // numpy: array * python float, the float converted to the array's dtype first
+    out[idx] = v;
+}
+
+// fmt 0: uint8, 1: int16, 2: int32, 3: float32 (gesture_dataset._demo_item's divisors); channel mean in numpy's float32 order:
+// left to right below eight channels, the pairwise tree at eight
+__global__ void __launch_bounds__(kThreads) clip_pcm_kernel(int fmt, const void* __restrict__ pcm, int64_t n, int channels, int64_t first,
+                                                            float* __restrict__ out) {
+    const int64_t i = (int64_t)blockIdx.x * kThreads + threadIdx.x;
+    if (i >= n - first) return;
+    const int64_t base = (first + i) * channels;
+    float r[8];
+#pragma unroll
+    for (int ch = 0; ch < 8; ++ch) {
+        float v = 0.f;
+        if (ch < channels) {
+            if (fmt == 0) v = ((float)((const uint8_t*)pcm)[base + ch] - 128.0f) / 128.0f;
+            else if (fmt == 1) v = (float)((const int16_t*)pcm)[base + ch] / 32768.0f;
+            else if (fmt == 2) v = (float)((const int32_t*)pcm)[base + ch] / 2147483648.0f;
+            else v = ((const float*)pcm)[base + ch];
+        }
+        r[ch] = v;
+    }
+    float sum;
+    if (channels == 8) {  // numpy's pairwise sum takes eight values as a tree
+        sum = ((r[0] + r[1]) + (r[2] + r[3])) + ((r[4] + r[5]) + (r[6] + r[7]));
+    } else {
+        sum = r[0];
+        for (int ch = 1; ch < channels; ++ch) sum = sum + r[ch];
+    }
+    out[i] = channels == 1 ? r[0] : sum / (float)channels;
+}
+
+// y[j] = sum over q of taps[k0 + up*q] * x[t/up - q], t = (j + n_pre_remove)*down, k0 = t % up: upfirdn's zero-extended sum in
+// ascending tap order.  One wave, one output per lane.  LDS: the taps of the tile's phases (all `up` phases when up <= kResTile:
+// staged once for every tile the block walks; else one phase per lane, staged per tile) and the input span of the tile.
+__global__ void __launch_bounds__(kResTile) clip_resample_kernel(const float* __restrict__ x, int64_t n_in, const double* __restrict__ taps,
+                                                                 int n_taps, int up, int down, int64_t n_pre_remove, int q_max, int span_max,
+                                                                 int tiles_per_block, float* __restrict__ y, int64_t n_out) {
+    extern __shared__ double res_lds[];
+    const int slots = up <= kResTile ? up : kResTile;
+    double* s_taps = res_lds;                              // [q][slot]
+    float* s_x = (float*)(res_lds + (size_t)q_max * slots);  // [span_max]
+    const int lane = threadIdx.x;
+    for (int r = 0; r < tiles_per_block; ++r) {
+        const int64_t j0 = ((int64_t)blockIdx.x * tiles_per_block + r) * kResTile;
+        if (j0 >= n_out) break;  // uniform
+        const int64_t j = j0 + lane;
+        const int64_t t = (j + n_pre_remove) * down;
+        const int k0 = (int)(t % up);
+        const int64_t ib = t / up;
+        const int slot = up <= kResTile ? k0 : lane;
+        if (r == 0 || up > kResTile) {
+            if (up <= kResTile) {
+                for (int e = lane; e < q_max * slots; e += kResTile) {
+                    const int q = e / slots, ph = e % slots;
+                    const int64_t k = (int64_t)ph + (int64_t)up * q;
+                    s_taps[e] = k < n_taps ? taps[k] : 0.0;
+                }
+            } else {
+                for (int q = 0; q < q_max; ++q) {
+                    const int64_t k = (int64_t)k0 + (int64_t)up * q;
+                    s_taps[q * slots + lane] = k < n_taps ? taps[k] : 0.0;
+                }
+            }
+        }
+        // input span of the tile: [lo, lo + span_max), lo = the lowest index any lane reads
+        const int64_t lo = ((j0 + n_pre_remove) * down) / up - (q_max - 1);
+        for (int e = lane; e < span_max; e += kResTile) {
+            const int64_t i = lo + e;
+            s_x[e] = (i >= 0 && i < n_in) ? x[i] : 0.f;
+        }
+        __syncthreads();
+        if (j < n_out) {
+            double acc = 0.0;
+            for (int q = 0; q < q_max; ++q) {
+                const int64_t i = ib - q;
+                if (i < 0) break;
+                if ((int64_t)k0 + (int64_t)up * q >= n_taps) break;
+                if (i >= n_in) continue;
+                const double prod = s_taps[q * slots + slot] * (double)s_x[(int)(i - lo)];
+                acc = acc + prod;
+            }
+            y[j] = (float)acc;
+        }
+        __syncthreads();
+    }
+}
+
+__global__ void __launch_bounds__(kThreads) clip_gather_audio_kernel(const float* __restrict__ audio, int64_t n_audio, const int64_t* __restrict__ a0,
+                                                                     const int64_t* __restrict__ a1, int64_t l_max, float* __restrict__ out,
+                                                                     int32_t* __restrict__ lengths) {
+    const int c = blockIdx.y;
+    const int64_t i = (int64_t)blockIdx.x * kThreads + threadIdx.x;
+    int64_t b = a0[c] < 0 ? 0 : a0[c], e = a1[c] < 0 ? 0 : a1[c];
+    b = b > n_audio ? n_audio : b;
+    e = e > n_audio ? n_audio : e;
+    const int64_t len = e > b ? e - b : 0;  // numpy's interval[a0:a1]: short or empty past the end
+    if (i == 0) lengths[c] = (int32_t)len;
+    if (i < l_max) out[(int64_t)c * l_max + i] = i < len ? audio[b + i] : 0.f;
+}
+
+struct ResPlan {
+    int q_max, span_max, slots, tiles_per_block;
+    int64_t lds;
+};
+
+bool res_plan(int n_taps, int up, int down, ResPlan* p) {
+    if (n_taps <= 0 || up <= 0 || down <= 0 || up > (1 << 20) || down > (1 << 20)) return false;
+    p->q_max = (n_taps + up - 1) / up;
+    p->slots = up <= kResTile ? up : kResTile;
+    // lanes of a tile read inputs [lo, hi]: lo = first lane's t/up - (q_max-1), hi = last lane's t/up
+    const int64_t span = ((int64_t)(kResTile - 1) * down + up - 1) / up + 1 + p->q_max;
+    if (span > (1 << 20)) return false;
+    p->span_max = (int)span;
+    p->tiles_per_block = up <= kResTile ? kResTilesPerBlock : 1;
+    p->lds = (int64_t)p->q_max * p->slots * (int64_t)sizeof(double) + (int64_t)p->span_max * (int64_t)sizeof(float);
+    return p->lds <= kResMaxLds;
+}
+
+}  // namespace
+
+extern "C" int64_t sdt_clip_workspace_bytes(int64_t n_frames) {
+    if (n_frames <= 0 || n_frames > (1 << 30)) return -1;
+    return cdiv64(n_frames, kThreads) * (int64_t)sizeof(int32_t);  // one count per block of window candidates (at most n_frames of them)
+}
+
+extern "C" int sdt_clip_frame_flags(int elem_bytes, const void* src, const void* present, int64_t n_frames, int32_t* keep, double* dist,
+                                    int32_t* bad, void* stream) {
+    SDT_CHECK_ARG(elem_bytes == 4 || elem_bytes == 8, "elem_bytes must be 4 (float32 keypoints) or 8 (float64 keypoints)");
+    SDT_CHECK_ARG(src != nullptr && present != nullptr && keep != nullptr && dist != nullptr && bad != nullptr, "null pointer");
+    SDT_CHECK_ARG(n_frames > 0 && n_frames <= (1 << 30), "bad frame count");
+    const unsigned grid = (unsigned)cdiv64(n_frames, (int64_t)kFramesPerWave * (kThreads / 64));
+    hipStream_t st = (hipStream_t)stream;
+    if (elem_bytes == 4)
+        hipLaunchKernelGGL((clip_frame_flags_kernel<float>), dim3(grid), dim3(kThreads), 0, st, (const float*)src, (const uint8_t*)present,
+                           n_frames, keep, dist, bad);
+    else
+        hipLaunchKernelGGL((clip_frame_flags_kernel<double>), dim3(grid), dim3(kThreads), 0, st, (const double*)src, (const uint8_t*)present,
+                           n_frames, keep, dist, bad);
+    SDT_LAUNCH_CHECK();
+    return SDT_OK;
+}
+
+extern "C" int sdt_clip_scan(const int32_t* keep, const double* dist, int64_t n_frames, int32_t* prefix, double* dist_kept, void* stream) {
+    SDT_CHECK_ARG(keep != nullptr && dist != nullptr && prefix != nullptr && dist_kept != nullptr, "null pointer");
+    SDT_CHECK_ARG(n_frames > 0 && n_frames <= (1 << 30), "bad frame count");
+    hipLaunchKernelGGL(clip_scan_kernel, dim3(1), dim3(kThreads), 0, (hipStream_t)stream, keep, dist, n_frames, prefix, dist_kept);
+    SDT_LAUNCH_CHECK();
+    return SDT_OK;
+}
+
+extern "C" int sdt_clip_shoulder_means(const double* dist_kept, const int32_t* prefix, int64_t n_frames, int chunks, double* means, void* stream) {
+    SDT_CHECK_ARG(dist_kept != nullptr && prefix != nullptr && means != nullptr, "null pointer");
+    SDT_CHECK_ARG(n_frames > 0 && n_frames <= (1 << 30), "bad frame count");
+    SDT_CHECK_ARG(chunks >= 1 && chunks <= 65536, "shoulder chunks must be in [1, 65536]");
+    hipLaunchKernelGGL(clip_shoulder_means_kernel, dim3((unsigned)cdiv(chunks, 64)), dim3(64), 0, (hipStream_t)stream, dist_kept, prefix, n_frames,
+                       chunks, means);
+    SDT_LAUNCH_CHECK();
+    return SDT_OK;
+}
+
+extern "C" int64_t sdt_clip_window_candidates(int64_t n_frames, int start_frame, int num_frames, int step) {
+    if (n_frames <= 0 || n_frames > (1 << 30) || start_frame < 0 || num_frames <= 0 || step <= 0) return -1;
+    const int64_t stop = n_frames - num_frames;  // range(start, n - F, step)
+    return stop > start_frame ? (stop - start_frame + step - 1) / step : 0;
+}
+
+extern "C" int sdt_clip_windows(const int32_t* prefix, int64_t n_frames, int start_frame, int num_frames, int step, void* workspace,
+                                int64_t workspace_bytes, int32_t* starts, int64_t starts_capacity, int32_t* n_clips, void* stream) {
+    SDT_CHECK_ARG(prefix != nullptr && workspace != nullptr && starts != nullptr && n_clips != nullptr, "null pointer");
+    const int64_t n_cand = sdt_clip_window_candidates(n_frames, start_frame, num_frames, step);
+    SDT_CHECK_ARG(n_cand >= 0, "bad frame count / start / window / step");
+    SDT_CHECK_ARG(starts_capacity >= n_cand, "starts buffer smaller than the candidate count");
+    SDT_CHECK_ARG(workspace_bytes >= sdt_clip_workspace_bytes(n_frames), "workspace too small");
+    hipStream_t st = (hipStream_t)stream;
+    if (n_cand == 0) {  // a video shorter than start + window: zero clips, nothing to launch but the count
+        if (hipMemsetAsync(n_clips, 0, sizeof(int32_t), st) != hipSuccess) return SDT_ERR_LAUNCH;
+        return SDT_OK;
+    }
+    const unsigned grid = (unsigned)cdiv64(n_cand, kThreads);
+    int32_t* counts = (int32_t*)workspace;
+    hipLaunchKernelGGL((clip_windows_kernel<false>), dim3(grid), dim3(kThreads), 0, st, prefix, n_cand, start_frame, step, num_frames, counts,
+                       starts, n_clips);
+    hipLaunchKernelGGL((clip_windows_kernel<true>), dim3(grid), dim3(kThreads), 0, st, prefix, n_cand, start_frame, step, num_frames, counts,
+                       starts, n_clips);
+    SDT_LAUNCH_CHECK();
+    return SDT_OK;
+}
+
+extern "C" int sdt_clip_gather_poses(int elem_bytes, const void* src, int64_t n_frames, const int32_t* starts, int64_t n_clips, int num_frames,
+                                     double scalar, int scale_confidence, void* out, int64_t out_elems, void* stream) {
+    SDT_CHECK_ARG(elem_bytes == 4 || elem_bytes == 8, "elem_bytes must be 4 or 8");
+    SDT_CHECK_ARG(src != nullptr && starts != nullptr && out != nullptr, "null pointer");
+    SDT_CHECK_ARG(n_frames > 0 && n_clips > 0 && num_frames > 0 && num_frames <= n_frames, "bad frame / clip / window count");
+    const int64_t total = n_clips * num_frames * kFrameElems;
+    SDT_CHECK_ARG(out_elems >= total, "output buffer too small");
+    SDT_CHECK_ARG(cdiv64(total, kThreads) <= 0x7fffffff, "too many clips for one launch");
+    const unsigned grid = (unsigned)cdiv64(total, kThreads);
+    hipStream_t st = (hipStream_t)stream;
+    if (elem_bytes == 4)
+        hipLaunchKernelGGL((clip_gather_poses_kernel<float>), dim3(grid), dim3(kThreads), 0, st, (const float*)src, n_frames, starts, total,
+                           num_frames, scalar, scale_confidence, (float*)out);
+    else
+        hipLaunchKernelGGL((clip_gather_poses_kernel<double>), dim3(grid), dim3(kThreads), 0, st, (const double*)src, n_frames, starts, total,
+                           num_frames, scalar, scale_confidence, (double*)out);
+    SDT_LAUNCH_CHECK();
+    return SDT_OK;
+}
+
+extern "C" int sdt_clip_pcm_to_mono_f32(int fmt, const void* pcm, int64_t n_samples, int channels, int64_t first, float* out, int64_t out_elems,
+                                        void* stream) {
+    SDT_CHECK_ARG(fmt >= 0 && fmt <= 3, "fmt must be 0 (uint8), 1 (int16), 2 (int32) or 3 (float32)");
+    SDT_CHECK_ARG(pcm != nullptr && out != nullptr, "null pointer");
+    SDT_CHECK_ARG(channels >= 1 && channels <= 8, "1 to 8 channels");
+    SDT_CHECK_ARG(n_samples > 0 && first >= 0 && first < n_samples, "cut outside the track");
+    SDT_CHECK_ARG(out_elems >= n_samples - first, "output buffer too small");
+    SDT_CHECK_ARG(cdiv64(n_samples - first, kThreads) <= 0x7fffffff, "track too long for one launch");
+    hipLaunchKernelGGL(clip_pcm_kernel, dim3((unsigned)cdiv64(n_samples - first, kThreads)), dim3(kThreads), 0, (hipStream_t)stream, fmt, pcm,
+                       n_samples, channels, first, out);
+    SDT_LAUNCH_CHECK();
+    return SDT_OK;
+}
+
+extern "C" int64_t sdt_clip_resample_lds_bytes(int n_taps, int up, int down) {
+    ResPlan p;
+    return res_plan(n_taps, up, down, &p) ? p.lds : -1;
+}
+
+extern "C" int sdt_clip_resample_f32(const float* x, int64_t n_in, const double* taps, int n_taps, int up, int down, int64_t n_pre_remove,
+                                     float* y, int64_t n_out, void* stream) {
+    SDT_CHECK_ARG(x != nullptr && taps != nullptr && y != nullptr, "null pointer");
+    ResPlan p;
+    SDT_CHECK_ARG(res_plan(n_taps, up, down, &p), "unsupported filter length / ratio");
+    SDT_CHECK_ARG(n_in > 0 && n_out > 0 && n_pre_remove >= 0, "bad lengths");
+    SDT_CHECK_ARG(n_in <= ((int64_t)1 << 40) / up && n_out + n_pre_remove <= ((int64_t)1 << 40) / down, "track too long");
+    const int64_t blocks = cdiv64(n_out, (int64_t)kResTile * p.tiles_per_block);
+    SDT_CHECK_ARG(blocks <= 0x7fffffff, "track too long for one launch");
+    hipLaunchKernelGGL(clip_resample_kernel, dim3((unsigned)blocks), dim3(kResTile), (size_t)p.lds, (hipStream_t)stream, x, n_in, taps, n_taps, up,
+                       down, n_pre_remove, p.q_max, p.span_max, p.tiles_per_block, y, n_out);
+    SDT_LAUNCH_CHECK();
+    return SDT_OK;
+}
+
+extern "C" int sdt_clip_gather_audio(const float* audio, int64_t n_audio, const int64_t* a0, const int64_t* a1, int64_t n_clips, int64_t l_max,
+                                     float* out, int64_t out_elems, int32_t* lengths, void* stream) {
+    SDT_CHECK_ARG(audio != nullptr && a0 != nullptr && a1 != nullptr && out != nullptr && lengths != nullptr, "null pointer");
+    SDT_CHECK_ARG(n_audio > 0 && n_clips > 0 && n_clips <= 65535 && l_max > 0 && l_max <= 0x7fffffff, "bad audio / clip / length count");
+    SDT_CHECK_ARG(out_elems >= n_clips * l_max, "output buffer too small");
+    hipLaunchKernelGGL(clip_gather_audio_kernel, dim3((unsigned)cdiv64(l_max, kThreads), (unsigned)n_clips), dim3(kThreads), 0, (hipStream_t)stream,
+                       audio, n_audio, a0, a1, l_max, out, lengths);
+    SDT_LAUNCH_CHECK();
+    return SDT_OK;
+}
