@@ -519,6 +519,36 @@ int sdt_code_pca_raster(const double* X, int64_t n_rows, const double* axis_limi
                         int margin, int marker_px, uint32_t* counts, int64_t counts_elems, uint8_t* out, int64_t out_bytes, void* stream);
 
 /*
+ * Principal template axes and nearest template codes (code_axes.py; DESIGN.md section 17 is the contract): what a user needs to pick the
+ * codes of the two demo modes (pose2pose.py:50-56 DEMO.CODE_PATH; voice2pose.py:107-117 DEMO.CODE_INDEX / CODE_INDEX_B).  x is the
+ * (n_rows, dim) fp32 table.  Supported sizes: 2 <= n_rows <= 2^30, 2 <= dim <= 64, 1 <= n_queries <= 65536, 1 <= n_ranks <= 16; outside
+ * them the workspace queries return 0 and the entry points SDT_ERR_UNSUPPORTED.  All arithmetic is float64 on values converted exactly
+ * from fp32, every operation rounded on its own; no floating-point atomics: the same bits on every call.  No allocation; every pointer
+ * is a device buffer; every index is checked against the sizes given.  Mean and covariance come from sdt_code_pca_moments.
+ *   eigh: as sdt_code_pca_eigh (the same device code), but comps is (dim, dim): every eigenvector, ranked by descending eigenvalue
+ *     (ties: the lower original column first), each signed so that its entry of largest magnitude (first of equals) is positive.
+ *     evals[0:2] and rows 0 and 1 of comps carry the bits sdt_code_pca_eigh returns.  0 <= max_sweeps <= 1000; info and err as there.
+ *   project: P (n_rows, dim) float64, P[n,k] = sum over d ascending of (x[n,d] - mean[d]) * comps[k,d]; columns 0 and 1 carry the bits
+ *     of sdt_code_pca_project's X.
+ *   quantiles: out (dim, n_ranks), out[k,r] = the element of column k of P that an ascending sort puts at position ranks[r]
+ *     (0 <= ranks[r] < n_rows, a device array of int64; the caller checks the range), by a radix select on the order-preserving uint64
+ *     image of the float64 bits: exact; -0.0 and +0.0 may come back as either zero.  Workspace:
+ *     sdt_code_axes_quantiles_workspace_bytes(n_rows, dim, n_ranks) bytes, never read before it is written.
+ *   nearest: d2(q, n) = sum over d ascending of (queries[q,d] - x[n,d])^2 with queries (n_queries, dim) float64; index[q] = the smallest
+ *     n that attains the minimum, dist2[q] = that minimum.  first_bad_query[0] = the first query with a non-finite entry, -1 if none;
+ *     such a query gets index -1 and dist2 NaN.  Workspace: sdt_code_axes_nearest_workspace_bytes(n_rows, dim, n_queries) bytes.
+ */
+int sdt_code_axes_eigh(const double* cov, int dim, int max_sweeps, double rel_tol, double* evals, double* comps, double* info, int32_t* err,
+                       void* stream);
+int sdt_code_axes_project(const float* x, int64_t n_rows, int dim, const double* mean, const double* comps, double* P, void* stream);
+int64_t sdt_code_axes_quantiles_workspace_bytes(int64_t n_rows, int dim, int n_ranks);
+int sdt_code_axes_quantiles(const double* P, int64_t n_rows, int dim, const int64_t* ranks, int n_ranks, double* out, void* workspace,
+                            int64_t workspace_bytes, void* stream);
+int64_t sdt_code_axes_nearest_workspace_bytes(int64_t n_rows, int dim, int64_t n_queries);
+int sdt_code_axes_nearest(const float* x, int64_t n_rows, int dim, const double* queries, int64_t n_queries, int64_t* index, double* dist2,
+                          int64_t* first_bad_query, void* workspace, int64_t workspace_bytes, void* stream);
+
+/*
  * The epoch-level validation metric, the Frechet gesture distance (core/utils/fgd.py:6-64, called from voice2pose.py:432-446; DESIGN.md
  * section 13 is the contract).  A feature row is row r of the fp32 (rows, d0) tensor x0 followed by row r of the fp32 (rows, d1) tensor
  * x1 (x1 NULL with d1 = 0); dim = d0 + d1, 2 <= dim <= 64.  All arithmetic is float64.  No allocation; every pointer except the two

@@ -183,6 +183,15 @@ def _canvas(text):
     return h, w
 
 
+def load_code_table(checkpoint, key=None):
+    """(key, table) of a checkpoint's code table: ``key`` of model_state_dict, or the first of CODE_KEYS that exists (host tensor)"""
+    sd = torch.load(checkpoint, map_location='cpu')['model_state_dict']
+    found = key or next((k for k in CODE_KEYS if k in sd), None)
+    if found is None or found not in sd:
+        raise KeyError('%s: no code table under %s' % (checkpoint, key or ' / '.join(CODE_KEYS)))
+    return found, sd[found]
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser(description="the clip-code PCA figure of a checkpoint (the reference's train/clip_code), drawn on the GPU")
     ap.add_argument('--checkpoint', required=True, help='a .pth of this engine or of the reference (same wire format)')
@@ -191,13 +200,10 @@ def main(argv=None):
     ap.add_argument('--canvas', type=_canvas, default=DEFAULT_CANVAS, help='HxW, default 480x640')
     ap.add_argument('--marker-px', type=int, default=2)
     a = ap.parse_args(argv)
-    sd = torch.load(a.checkpoint, map_location='cpu')['model_state_dict']
-    key = a.key or next((k for k in CODE_KEYS if k in sd), None)
-    if key is None or key not in sd:
-        raise KeyError('%s: no code table under %s' % (a.checkpoint, a.key or ' / '.join(CODE_KEYS)))
+    key, table = load_code_table(a.checkpoint, a.key)
     if not torch.cuda.is_available():
         raise RuntimeError('the clip-code figure is computed on the GPU (csrc/code_pca.hip); there is no CPU fallback')
-    image, meta = clip_code_figure(sd[key].float().cuda(), canvas=a.canvas, marker_px=a.marker_px, return_meta=True)
+    image, meta = clip_code_figure(table.float().cuda(), canvas=a.canvas, marker_px=a.marker_px, return_meta=True)
     meta['key'] = key
     save_png(a.out, image, meta)
     print('%s %s (%d, %d): %s -> %s' % (a.checkpoint, key, meta['n_rows'], meta['dim'], describe(meta), a.out))
