@@ -685,6 +685,30 @@ int sdt_clip_resample_f32(const float* x, int64_t n_in, const double* taps, int 
 int sdt_clip_gather_audio(const float* audio, int64_t n_audio, const int64_t* a0, const int64_t* a1, int64_t n_clips, int64_t l_max,
                           float* out, int64_t out_elems, int32_t* lengths, void* stream);
 
+/*
+ * Optimiser-side safeguards of the flat-buffer Adam (no counterpart in the reference): gradient-norm clipping as
+ * torch.nn.utils.clip_grad_norm_(norm_type=2, error_if_nonfinite=False), a step that a non-finite gradient cannot poison, and an
+ * exponential moving average of the parameters.  No atomics, no host read-back: hipGraph-capturable like the rest.
+ *   grad_sumsq_f64: partial[0] = sum of the float64 squares of g[0..n) in ONE fixed order (csrc/optim_guard.hip states it;
+ *     optim.sumsq_model is the same order in numpy, bit for bit); partial: sdt_grad_sumsq_partials() doubles, contents irrelevant.
+ *     Non-finite exactly when an element of g is.  g 16-byte aligned.
+ *   optim_guard_prep: partials = HOST array of n_buffers (1..4) device partial buffers, summed in argument order.  Writes the guard
+ *     record, 32 device bytes {double norm; float scale; int32 skip; int64 skipped; int64 reserved} zero-initialised by the caller:
+ *     norm = grad_scale * sqrt(sum); scale = (float)(grad_scale * coef), coef = min(max_norm / (norm + 1e-6), 1) in float64 (a NaN
+ *     stays a NaN), coef = 1 when max_norm <= 0; skip = skip_nonfinite and norm is not finite; skipped += skip.
+ *   adam_step_guarded_f32: sdt_adam_step_f32 with grad_scale read from the record.  skip set: nothing is written -- p, m, v, ema and
+ *     state_dev keep their bits.  ema != NULL: ema = ema_decay * ema + (1 - ema_decay) * p_new in the same pass (ema_decay in (0, 1)).
+ *   optim_guard_pass_elems: elements one grid pass of the launch as built covers (0: the sum of squares, 1: the guarded Adam step).
+ */
+int64_t sdt_grad_sumsq_partials(void);
+int64_t sdt_optim_guard_pass_elems(int which);
+int sdt_grad_sumsq_f64(const float* g, int64_t n, double* partial, void* stream);
+int sdt_optim_guard_prep(const double* const* partials, int n_buffers, float grad_scale, double max_norm, int skip_nonfinite,
+                         void* guard, void* stream);
+int sdt_adam_step_guarded_f32(float* p, const float* g, float* m, float* v, int64_t n, const float* lr_dev, float beta1, float beta2,
+                              float eps, float weight_decay, const void* guard, float* ema, float ema_decay, void* state_dev,
+                              void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -158,6 +158,11 @@ SIGNATURES = {
     "sdt_clip_resample_lds_bytes": [_i, _i, _i],  # (returns int64_t: restype set in load())
     "sdt_clip_resample_f32": [_p, _i64, _p, _i, _i, _i, _i64, _p, _i64, _p],
     "sdt_clip_gather_audio": [_p, _i64, _p, _p, _i64, _i64, _p, _i64, _p, _p],
+    "sdt_grad_sumsq_partials": [],  # (returns int64_t: restype set in load())
+    "sdt_optim_guard_pass_elems": [_i],  # (returns int64_t: restype set in load())
+    "sdt_grad_sumsq_f64": [_p, _i64, _p, _p],
+    "sdt_optim_guard_prep": [C.POINTER(C.c_void_p), _i, _f, C.c_double, _i, _p, _p],
+    "sdt_adam_step_guarded_f32": [_p, _p, _p, _p, _i64, _p, _f, _f, _f, _f, _p, _p, _f, _p, _p],
 }
 F32, BF16 = 0, 1  # enum sdt_dtype
 
@@ -211,6 +216,8 @@ def load():
     lib.sdt_clip_workspace_bytes.restype = C.c_int64
     lib.sdt_clip_window_candidates.restype = C.c_int64
     lib.sdt_clip_resample_lds_bytes.restype = C.c_int64
+    lib.sdt_grad_sumsq_partials.restype = C.c_int64
+    lib.sdt_optim_guard_pass_elems.restype = C.c_int64
     lib.sdt_conv_dw_group_plan_bytes.argtypes = [_i]
     lib.sdt_conv_dw_group_plan_bytes.restype = C.c_int64
     lib.sdt_conv_dw_workspace_bytes.argtypes = [_G]

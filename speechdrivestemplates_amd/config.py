@@ -36,7 +36,18 @@ _DEFAULTS = {
     },
     "TRAIN": {"NUM_EPOCHS": 100, "BATCH_SIZE": 32, "SAVE_VIDEO": True, "SAVE_NPZ": False, "LR": 1e-4, "WD": 0,
               "LR_SCHEDULER": True, "PRETRAIN_FROM": None, "VALIDATE": True, "NUM_RESULT_SAMPLE": 2,
-              "CHECKPOINT_INTERVAL": 1},
+              "CHECKPOINT_INTERVAL": 1,
+              # extensions (optimiser-side safeguards, optim.StepGuard / csrc/optim_guard.hip; all off by default = the
+              # step as it was).  Step groups are what optimizer_updates steps together: {optimizerClipCode, optimizerG} and {optimizerD_pose}.
+              # GRAD_CLIP_NORM: a positive float clips the global L2 norm of each step group's gradient to it, as
+              # torch.nn.utils.clip_grad_norm_(norm_type=2, error_if_nonfinite=False) does: coefficient max_norm / (norm + 1e-6), at most 1.
+              # SKIP_NONFINITE_STEP True: a step group whose gradient norm is not finite is not applied (parameters, moments, step counter
+              # and EMA keep their bits; a device counter goes up).  False: such a gradient makes the parameters NaN, as in torch.
+              # Either key also logs grad_norm_G / grad_norm_D (before clipping) and skipped_steps_G / skipped_steps_D with the losses.
+              # EMA_DECAY: d in (0, 1) keeps ema = d * ema + (1 - d) * p of the generator-side parameters (optimizerG, optimizerClipCode;
+              # pose2pose's optimiser), updated after every applied step and saved as 'model_ema_state_dict'.  The discriminator and the
+              # BatchNorm running statistics (buffers) are not averaged.
+              "GRAD_CLIP_NORM": None, "SKIP_NONFINITE_STEP": False, "EMA_DECAY": None},
     "TEST": {"BATCH_SIZE": 32, "NUM_RESULT_SAMPLE": 8, "SAVE_VIDEO": True, "SAVE_NPZ": True, "MULTIPLE": 1},
     "DEMO": {"MULTIPLE": 1, "NUM_SAMPLES": 1, "CODE_INDEX": None, "CODE_INDEX_B": None, "CODE_PATH": None},
     "SYS": {"OUTPUT_DIR": "output/", "CANVAS_SIZE": (720, 1280), "VISUALIZATION_SCALING": 0.85,
@@ -77,7 +88,10 @@ _DEFAULTS = {
             # DDP_UNSYNCED_D True = the reference's data-parallel quirk (core/pipelines/voice2pose.py:301,308): DistributedDataParallel
             # all-reduces the gradients of the FIRST backward of a step only, so the discriminator's own backward (the second one of an s2g step)
             # leaves per-rank gradients and the rank's discriminators drift apart.  Default False: this engine synchronises them (dp.GradReducer).
-            "DDP_UNSYNCED_D": False},
+            "DDP_UNSYNCED_D": False,
+            # EVAL_WITH_EMA True = validate(), test() and demo() run on the EMA weights (TRAIN.EMA_DECAY, or a checkpoint that carries
+            # 'model_ema_state_dict'); the training weights are back, bit for bit, when they return.  False = the training weights.
+            "EVAL_WITH_EMA": False},
 }
 
 
@@ -141,6 +155,18 @@ class CfgNode(dict):
                 except (ValueError, SyntaxError):
                     pass
             node[parts[-1]] = val
+
+
+def check_optim_guard(cfg, checkpoint_has_ema=False):
+    """Validate the optimiser-safeguard keys; ``checkpoint_has_ema``: the checkpoint being loaded carries 'model_ema_state_dict'."""
+    clip, decay = cfg.TRAIN.GRAD_CLIP_NORM, cfg.TRAIN.EMA_DECAY
+    if clip is not None and (isinstance(clip, bool) or not isinstance(clip, (int, float)) or not clip > 0):
+        raise ValueError("TRAIN.GRAD_CLIP_NORM must be None or a positive number, got %r" % (clip,))
+    if decay is not None and (isinstance(decay, bool) or not isinstance(decay, (int, float)) or not 0 < decay < 1):
+        raise ValueError("TRAIN.EMA_DECAY must be None or a number in (0, 1), got %r" % (decay,))
+    if cfg.SYS.EVAL_WITH_EMA and decay is None and not checkpoint_has_ema:
+        raise ValueError("SYS.EVAL_WITH_EMA needs an EMA to evaluate: set TRAIN.EMA_DECAY, or load a checkpoint that carries "
+                         "'model_ema_state_dict' (one written by a run with TRAIN.EMA_DECAY)")
 
 
 def get_cfg_defaults():

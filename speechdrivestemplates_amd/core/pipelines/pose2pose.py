@@ -66,6 +66,7 @@ class Pose2Pose(Trainer):
             self.schedulers['scheduler'] = _MultiStepLR(opt, [E - 10, E - 2], 0.1, last_epoch)
         self._set_reducer(dp.GradReducer(self.optimizers.values()))
         dp.sync_replicas(self.model, list(self.optimizers.values()))  # DDP-constructor semantics (pose2pose.py:102)
+        self.setup_step_guards({'G': ('optimizer',)}, ('optimizer',), checkpoint)
 
     def forward_backward(self, batch, want_final=False):
         dev = self.model.clip_code_mu.device
@@ -99,7 +100,7 @@ class Pose2Pose(Trainer):
     def optimizer_updates(self, losses):
         opt = self.optimizers['optimizer']
         self.reducer.all_reduce([opt])
-        opt.step()
+        self.guarded_steps('G', [opt], losses)
 
     def train_step(self, batch, t_step, global_step, epoch):
         # SYS.HIP_GRAPH: ~150 launches of a few microseconds -- enqueued one by one the step is bound by the host (3 ms); replayed from a hipGraph

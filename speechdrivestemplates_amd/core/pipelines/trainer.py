@@ -4,6 +4,7 @@ checkpoint wire format (:305-321), epoch loop (:367-405) and validation (:407-42
 SYS.TENSORBOARD, to a TensorBoard event file under the reference's tags (tb_events.py; :242-303).  Pose videos and long images are drawn on
 the GPU (render.py) and written by video.VideoWriter when SYS.RENDER_VIDEO is set (opt-in; default: npz only).  The per-epoch
 clip-code figure (:404-405, 281-283) is drawn on the GPU (code_pca.py) and written as a PNG when SYS.EPOCH_FIGURES is set."""
+import contextlib
 import logging
 import os
 import time
@@ -120,7 +121,15 @@ class Trainer(object):
             if checkpoint is None:
                 raise Exception('Checkpoint file is not provided.')
             assert checkpoint.split('.')[-1] == 'pth', 'file type not supported: %s' % checkpoint
-            self.setup_model(self.cfg, state_dict=torch.load(checkpoint, map_location='cpu')['model_state_dict'])
+            ckpt = torch.load(checkpoint, map_location='cpu')
+            key = 'model_state_dict'
+            if getattr(self.cfg.SYS, 'EVAL_WITH_EMA', False):  # test() / demo() build no optimiser: the EMA weights are loaded directly
+                if 'model_ema_state_dict' not in ckpt:
+                    raise ValueError("SYS.EVAL_WITH_EMA: the checkpoint %s carries no 'model_ema_state_dict' (it was not written by a "
+                                     "run with TRAIN.EMA_DECAY)" % checkpoint)
+                key = 'model_ema_state_dict'
+            self.setup_model(self.cfg, state_dict=ckpt[key])
+            self._model_holds_ema = key == 'model_ema_state_dict'
             return base_path
         self.setup_dataset(self.cfg, 'train')
         if resume_from is not None:
@@ -149,7 +158,84 @@ class Trainer(object):
                 'model_state_dict': {'module.' + k: v.detach().clone().contiguous() for k, v in self.model.state_dict().items()}}
         for k, v in self.optimizers.items():
             ckpt['%s_state_dict' % k] = v.state_dict()
+        ema = self.ema_model_state()
+        if ema is not None:
+            ckpt['model_ema_state_dict'] = ema
         return ckpt
+
+    # -- optimiser-side safeguards (TRAIN.GRAD_CLIP_NORM / SKIP_NONFINITE_STEP / EMA_DECAY, SYS.EVAL_WITH_EMA) ------
+    def setup_step_guards(self, groups, ema_names, checkpoint=None):
+        """``groups``: {'G': [optimiser names stepped together], 'D': [...]} -> one optim.StepGuard per group when clipping or the
+        non-finite skip is configured (self.step_guards, else empty: the step calls what it always called); ``ema_names``: the
+        optimisers whose parameters get an EMA with TRAIN.EMA_DECAY, restored from ``checkpoint['model_ema_state_dict']`` on resume
+        (a checkpoint without it: the EMA starts from the loaded weights).  Call after the replicas are synchronised."""
+        from ...config import check_optim_guard
+        from ...optim import StepGuard
+        cfg = self.cfg
+        check_optim_guard(cfg, checkpoint is not None and 'model_ema_state_dict' in checkpoint)
+        self.step_guards = {}
+        clip, skip = cfg.TRAIN.GRAD_CLIP_NORM, bool(cfg.TRAIN.SKIP_NONFINITE_STEP)
+        if clip is not None or skip:
+            for tag, names in groups.items():
+                opts = [self.optimizers[n] for n in names if n in self.optimizers]
+                if opts:
+                    self.step_guards[tag] = StepGuard(opts, max_norm=clip, skip_nonfinite=skip)
+        if cfg.TRAIN.EMA_DECAY is not None:
+            for n in ema_names:
+                if n in self.optimizers:
+                    self.optimizers[n].enable_ema(cfg.TRAIN.EMA_DECAY)
+            if checkpoint is not None and 'model_ema_state_dict' in checkpoint:
+                self.load_ema_model_state(checkpoint['model_ema_state_dict'])
+
+    def guarded_steps(self, tag, opts, losses):
+        """guard (norm -> record) -> steps of one step group, after its gradient exchange; the device scalars join the loss dict"""
+        guard = getattr(self, 'step_guards', {}).get(tag)
+        if guard is not None:
+            guard.prepare()
+            losses['grad_norm_' + tag], losses['skipped_steps_' + tag] = guard.norm(), guard.skipped()
+        for opt in opts:
+            opt.step()
+
+    def _ema_params(self):
+        """[(state_dict key, optimiser, index)] of every parameter that has an EMA"""
+        owner = {id(p): (opt, i) for opt in self.optimizers.values() if opt.ema is not None for i, p in enumerate(opt.params)}
+        return [(name,) + owner[id(p)] for name, p in self.model.named_parameters() if id(p) in owner]
+
+    def ema_model_state(self):
+        """``model_state_dict`` with the averaged parameters replaced by their EMA (same keys; None: no optimiser keeps an EMA)"""
+        ema = self._ema_params()
+        if not ema:
+            return None
+        out = {'module.' + k: v.detach().clone().contiguous() for k, v in self.model.state_dict().items()}
+        for name, opt, i in ema:
+            out['module.' + name] = opt._per_param(opt.ema, i).detach().clone().contiguous()
+        return out
+
+    def load_ema_model_state(self, sd):
+        sd = {(k[len('module.'):] if k.startswith('module.') else k): v for k, v in sd.items()}
+        with torch.no_grad():
+            for name, opt, i in self._ema_params():
+                if name in sd:
+                    opt._per_param(opt.ema, i).copy_(sd[name])
+
+    @contextlib.contextmanager
+    def eval_weights(self):
+        """SYS.EVAL_WITH_EMA: the EMA weights are in the parameter buffers inside the block and the training weights are back, bit
+        for bit, after it -- also when the block raises.  Without the key: nothing happens."""
+        if not getattr(self.cfg.SYS, 'EVAL_WITH_EMA', False) or getattr(self, '_model_holds_ema', False):
+            yield
+            return
+        opts = [opt for opt in self.optimizers.values() if opt.ema is not None]
+        if not opts:
+            raise ValueError('SYS.EVAL_WITH_EMA needs an EMA to evaluate: set TRAIN.EMA_DECAY (or test / demo from a checkpoint that '
+                             "carries 'model_ema_state_dict')")
+        for opt in opts:
+            opt.swap_ema()  # (marks the weight mirrors dirty)
+        try:
+            yield
+        finally:
+            for opt in opts:
+                opt.swap_ema()
 
     @staticmethod
     def check_kernels():
@@ -384,6 +470,10 @@ class Trainer(object):
         """trainer.py:407-427 (same positional signature).  Data-parallel runs first take rank 0's buffers (dp.sync_buffers):
         eval-mode BatchNorm then reads the same running statistics on every rank, as under DDP's per-forward buffer
         broadcast."""
+        with self.eval_weights():
+            return self._validate(test_dataloader, epoch, tag)
+
+    def _validate(self, test_dataloader, epoch, tag):
         from ... import dp
         test_dataloader = self.test_dataloader if test_dataloader is None else test_dataloader
         self.apply_knobs()
@@ -429,6 +519,10 @@ class Trainer(object):
         self.setup_video_writer()
         self.setup_tb_writer()
         self.model.eval()
+        with self.eval_weights():
+            return self._demo_steps()
+
+    def _demo_steps(self):
         out = []
         for t_step, batch in enumerate(self.test_dataloader):
             m = self.cfg.DEMO.MULTIPLE

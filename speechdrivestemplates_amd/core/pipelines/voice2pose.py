@@ -224,6 +224,9 @@ class Voice2Pose(Trainer):
             self.optimizers['optimizerD_pose'].grad_scale = 1.0
         # DDP-constructor semantics (voice2pose.py:222-223): every rank starts from rank 0's parameters, buffers and Adam state
         dp.sync_replicas(self.model, list(self.optimizers.values()))
+        # clipping / non-finite skip per step group, EMA of the generator side (after the sync: the EMA starts from rank 0's weights)
+        self.setup_step_guards({'G': ('optimizerClipCode', 'optimizerG'), 'D': ('optimizerD_pose',)},
+                               ('optimizerClipCode', 'optimizerG'), checkpoint)
         if self.reducer.active:
             # Gradient buckets in the order backward completes them (the flat buffer is laid out audio encoder L0..L7,
             # U-Net, decoder): [U-Net + decoder, ~14 MB] when backward reaches the audio encoder, then [L5..L7, ~11 MB],
@@ -294,19 +297,18 @@ class Voice2Pose(Trainer):
         return losses, results
 
     def optimizer_updates(self, losses):
-        """Gradient all-reduce + Adam steps (voice2pose.py:302-309)."""
+        """Gradient all-reduce + (guard +) Adam steps (voice2pose.py:302-309)."""
         has_d = 'optimizerD_pose' in self.optimizers
         group = [self.optimizers[k] for k in ('optimizerClipCode', 'optimizerG') if k in self.optimizers]
         self.reducer.all_reduce(group)
-        for opt in group:
-            opt.step()
+        self.guarded_steps('G', group, losses)
         if has_d:
             optd = self.optimizers['optimizerD_pose']
             optd.zero_grad()
             losses['D_pose_gan_loss'].backward()
             if not getattr(self, 'unsynced_d', False):  # (SYS.DDP_UNSYNCED_D: the reference's second backward is not exchanged)
                 self.reducer.all_reduce([optd])
-            optd.step()
+            self.guarded_steps('D', [optd], losses)
 
     def train_step(self, batch, t_step, global_step, epoch):
         tag = 'TRAIN'

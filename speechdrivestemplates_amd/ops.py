@@ -2019,3 +2019,52 @@ def adam_step(p, g, m, v, lr_dev, state_dev, beta1=0.9, beta2=0.999, eps=1e-8, w
     _req_cuda(p, g, m, v, lr_dev, state_dev)
     check(_lib.load().sdt_adam_step_f32(_p(p), _p(g), _p(m), _p(v), p.numel(), _p(lr_dev), beta1, beta2, eps, weight_decay,
                                         grad_scale, _p(state_dev), _stream()))
+
+
+# --------------------------------------------------------------------------------------------
+# Optimiser-side safeguards (csrc/optim_guard.hip)
+GUARD_WORDS = 4  # the guard record as int64 words: {f64 norm | f32 scale, i32 skip | i64 skipped | reserved}
+
+
+def grad_sumsq_partials():
+    """float64 elements the ``partial`` buffer of ``grad_sumsq`` needs"""
+    return int(_lib.load().sdt_grad_sumsq_partials())
+
+
+def optim_guard_pass_elems(which):
+    """elements ONE grid pass of the launch as built covers: 'sumsq' or 'adam' (the guarded step)"""
+    return int(_lib.load().sdt_optim_guard_pass_elems({'sumsq': 0, 'adam': 1}[which]))
+
+
+def grad_sumsq(g, partial):
+    """partial[0] = ordered float64 sum of squares of the fp32 buffer ``g`` (bit-identical to optim.sumsq_model)"""
+    _req_cuda(g, partial)
+    if g.dtype != torch.float32 or partial.dtype != torch.float64 or partial.numel() < grad_sumsq_partials():
+        raise ValueError('grad_sumsq: g must be fp32 and partial %d float64 elements' % grad_sumsq_partials())
+    check(_lib.load().sdt_grad_sumsq_f64(_p(g), g.numel(), _p(partial), _stream()))
+    return partial
+
+
+def optim_guard_prep(partials, guard, grad_scale=1.0, max_norm=0.0, skip_nonfinite=False):
+    """Combine up to four buffers' sums of squares (argument order) into the device guard record: pre-clip norm, effective gradient
+    scale, skip flag, skip counter.  ``max_norm`` <= 0: no clipping."""
+    _req_cuda(guard, *partials)
+    if not 1 <= len(partials) <= 4:
+        raise ValueError('a step group has 1 to 4 buffers, got %d' % len(partials))
+    if guard.dtype != torch.int64 or guard.numel() < GUARD_WORDS:
+        raise ValueError('the guard record is %d int64 words' % GUARD_WORDS)
+    import ctypes as C
+    arr = (C.c_void_p * len(partials))(*[_p(t) for t in partials])
+    check(_lib.load().sdt_optim_guard_prep(arr, len(partials), grad_scale, float(max_norm), int(bool(skip_nonfinite)), _p(guard), _stream()))
+
+
+def adam_step_guarded(p, g, m, v, lr_dev, state_dev, guard, beta1=0.9, beta2=0.999, eps=1e-8, weight_decay=0.0, ema=None, ema_decay=0.0):
+    """``adam_step`` with the gradient scale and the skip decision read from the guard record; ``ema``: the EMA of the new parameters in
+    the same pass."""
+    _req_cuda(p, g, m, v, lr_dev, state_dev, guard)
+    if ema is not None:
+        _req_cuda(ema)
+        if ema.numel() != p.numel() or ema.dtype != torch.float32:
+            raise ValueError('the EMA buffer must match the parameter buffer')
+    check(_lib.load().sdt_adam_step_guarded_f32(_p(p), _p(g), _p(m), _p(v), p.numel(), _p(lr_dev), beta1, beta2, eps, weight_decay,
+                                                _p(guard), _p(ema), ema_decay, _p(state_dev), _stream()))
