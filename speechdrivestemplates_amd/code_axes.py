@@ -21,7 +21,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from .code_pca import MAX_DIM, MAX_SWEEPS, REL_TOL, _as_table, load_code_table
+from .code_pca import MAX_DIM, MAX_SWEEPS, REL_TOL, _as_table, _eigh_decode, _eigh_launch, _moments, load_code_table
 
 MAX_QUERIES = 65536
 MAX_RANKS = 16
@@ -40,23 +40,6 @@ def _check(status):
     _lib.check(status)
 
 
-def _moments(lib, x, raw):
-    """mean, covariance of the table by sdt_code_pca_moments; raises on a non-finite row BEFORE any other kernel sees the table"""
-    n, d = x.shape
-    ws_bytes = lib.sdt_code_pca_workspace_bytes(n, d)
-    if ws_bytes <= 0:
-        raise ValueError('unsupported table size (%d, %d)' % (n, d))
-    f64 = dict(dtype=torch.float64, device=x.device)
-    ws = torch.empty(ws_bytes // 8, **f64)
-    mean, cov = torch.empty(d, **f64), torch.empty((d, d), **f64)
-    bad = torch.empty(1, dtype=torch.int64, device=x.device)
-    _lib.check(lib.sdt_code_pca_moments(_p(x), n, d, _p(ws), ws_bytes, _p(mean), _p(cov), _p(bad), raw))
-    row = int(bad.item())
-    if row:
-        raise ValueError('the code table has a non-finite entry in row %d' % (row - 1))
-    return mean, cov
-
-
 def fit_axes(codes, max_sweeps=MAX_SWEEPS):
     """All principal axes of the (N, D) / (N, F, D) fp32 device table ``codes`` and its projection on them.
     -> {'mean' (D,), 'components' (D, D), 'explained_variance' (D,), 'explained_variance_ratio' (D,), 'projections' (N, D),
@@ -69,21 +52,13 @@ def fit_axes(codes, max_sweeps=MAX_SWEEPS):
     with torch.cuda.device(dev):
         raw = torch.cuda.current_stream(dev).cuda_stream
         mean, cov = _moments(lib, x, raw)
-        f64 = dict(dtype=torch.float64, device=dev)
-        evals, comps, info = torch.empty(d, **f64), torch.empty((d, d), **f64), torch.empty(4, **f64)
-        err = torch.empty(1, dtype=torch.int32, device=dev)
-        proj = torch.empty((n, d), **f64)
-        _check(lib.sdt_code_axes_eigh(_p(cov), d, int(max_sweeps), REL_TOL, _p(evals), _p(comps), _p(info), _p(err), raw))
-        word = int(err.item())
-        sweeps, offdiag, frob, trace = info.cpu().tolist()
-        if word & 1:
-            raise RuntimeError('Jacobi did not converge in %d sweeps: off-diagonal norm %.3e, ||C||_F %.3e' % (max_sweeps, offdiag, frob))
-        if word & 2:
-            raise ValueError('the code table has no variance (trace of its covariance is %r): every row is the same' % trace)
+        evals, comps, info, err = _eigh_launch(lib, 'axes', cov, d, max_sweeps, raw, check=_check)
+        sweeps, offdiag, _, trace = _eigh_decode(max_sweeps, info, err)
+        proj = torch.empty((n, d), dtype=torch.float64, device=dev)
         _check(lib.sdt_code_axes_project(_p(x), n, d, _p(mean), _p(comps), _p(proj), raw))
         ratio = torch.from_numpy(evals.cpu().numpy() / trace).to(dev)
     return {'mean': mean, 'components': comps, 'explained_variance': evals, 'explained_variance_ratio': ratio, 'projections': proj,
-            'covariance': cov, 'sweeps': int(sweeps), 'offdiag': offdiag, 'n_rows': n, 'dim': d}
+            'covariance': cov, 'sweeps': sweeps, 'offdiag': offdiag, 'n_rows': n, 'dim': d}
 
 
 def quantile_ranks(q, n):

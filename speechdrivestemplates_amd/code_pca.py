@@ -68,6 +68,45 @@ def _as_table(codes):
     return codes.detach().contiguous()
 
 
+def _moments(lib, x, raw):
+    """mean, covariance of the table by sdt_code_pca_moments; raises on a non-finite row BEFORE any other kernel sees the table"""
+    n, d = x.shape
+    ws_bytes = lib.sdt_code_pca_workspace_bytes(n, d)
+    if ws_bytes <= 0:
+        raise ValueError('unsupported table size (%d, %d)' % (n, d))
+    f64 = dict(dtype=torch.float64, device=x.device)
+    ws = torch.empty(ws_bytes // 8, **f64)
+    mean, cov = torch.empty(d, **f64), torch.empty((d, d), **f64)
+    bad = torch.empty(1, dtype=torch.int64, device=x.device)
+    _lib.check(lib.sdt_code_pca_moments(_p(x), n, d, _p(ws), ws_bytes, _p(mean), _p(cov), _p(bad), raw))
+    row = int(bad.item())
+    if row:
+        raise ValueError('the code table has a non-finite entry in row %d' % (row - 1))
+    return mean, cov
+
+
+def _eigh_launch(lib, which, cov, n_comps, max_sweeps, raw, check=_lib.check):
+    """queues sdt_code_<which>_eigh ('pca' or 'axes') on the (D, D) device covariance -> (evals, comps, info, err), unread device tensors"""
+    d = cov.shape[0]
+    f64 = dict(dtype=torch.float64, device=cov.device)
+    evals, comps, info = torch.empty(d, **f64), torch.empty((n_comps, d), **f64), torch.empty(4, **f64)
+    err = torch.empty(1, dtype=torch.int32, device=cov.device)
+    fn = getattr(lib, 'sdt_code_%s_eigh' % which)
+    check(fn(_p(cov), d, int(max_sweeps), REL_TOL, _p(evals), _p(comps), _p(info), _p(err), raw))
+    return evals, comps, info, err
+
+
+def _eigh_decode(max_sweeps, info, err):
+    """reads the error word and info of a queued ``_eigh_launch`` -> (sweeps, offdiag, frob, trace); raises what the word says"""
+    word = int(err.item())
+    sweeps, offdiag, frob, trace = info.cpu().tolist()
+    if word & 1:
+        raise RuntimeError('Jacobi did not converge in %d sweeps: off-diagonal norm %.3e, ||C||_F %.3e' % (max_sweeps, offdiag, frob))
+    if word & 2:
+        raise ValueError('the code table has no variance (trace of its covariance is %r): every row is the same' % trace)
+    return int(sweeps), offdiag, frob, trace
+
+
 def fit_project(codes, max_sweeps=MAX_SWEEPS):
     """2-component PCA of the (N, D) / (N, F, D) fp32 device table ``codes`` and its projection.
     -> {'mean' (D,), 'components' (2, D), 'explained_variance' (2,), 'explained_variance_ratio' (2,), 'eigenvalues' (D,): numpy
@@ -79,33 +118,18 @@ def fit_project(codes, max_sweeps=MAX_SWEEPS):
     dev = x.device
     with torch.cuda.device(dev):
         raw = torch.cuda.current_stream(dev).cuda_stream
-        ws_bytes = lib.sdt_code_pca_workspace_bytes(n, d)
-        if ws_bytes <= 0:
-            raise ValueError('unsupported table size (%d, %d)' % (n, d))
+        mean, cov = _moments(lib, x, raw)
+        evals, comps, info, err = _eigh_launch(lib, 'pca', cov, 2, max_sweeps, raw)
         f64 = dict(dtype=torch.float64, device=dev)
-        ws = torch.empty(ws_bytes // 8, **f64)
-        mean, cov = torch.empty(d, **f64), torch.empty((d, d), **f64)
-        bad = torch.empty(1, dtype=torch.int64, device=dev)
-        _lib.check(lib.sdt_code_pca_moments(_p(x), n, d, _p(ws), ws_bytes, _p(mean), _p(cov), _p(bad), raw))
-        row = int(bad.item())
-        if row:
-            raise ValueError('the code table has a non-finite entry in row %d' % (row - 1))
-        evals, comps, info = torch.empty(d, **f64), torch.empty((2, d), **f64), torch.empty(4, **f64)
-        err = torch.empty(1, dtype=torch.int32, device=dev)
-        X, limits = torch.empty((n, 2), **f64), torch.empty(8, **f64)
-        _lib.check(lib.sdt_code_pca_eigh(_p(cov), d, int(max_sweeps), REL_TOL, _p(evals), _p(comps), _p(info), _p(err), raw))
-        _lib.check(lib.sdt_code_pca_project(_p(x), n, d, _p(mean), _p(comps), _p(X), _p(ws), ws_bytes, _p(limits), raw))
-        word = int(err.item())
-        sweeps, offdiag, frob, trace = info.cpu().tolist()
-    if word & 1:
-        raise RuntimeError('Jacobi did not converge in %d sweeps: off-diagonal norm %.3e, ||C||_F %.3e' % (max_sweeps, offdiag, frob))
-    if word & 2:
-        raise ValueError('the code table has no variance (trace of its covariance is %r): every row is the same' % trace)
+        ws_bytes = lib.sdt_code_pca_workspace_bytes(n, d)
+        ws, X, limits = torch.empty(ws_bytes // 8, **f64), torch.empty((n, 2), **f64), torch.empty(8, **f64)
+        _lib.check(lib.sdt_code_pca_project(_p(x), n, d, _p(mean), _p(comps), _p(X), _p(ws), ws_bytes, _p(limits), raw))  # queued before the error word is read
+        sweeps, offdiag, frob, trace = _eigh_decode(max_sweeps, info, err)
     lam = evals.cpu().numpy()
     lim = limits.cpu().tolist()
     return {'mean': mean.cpu().numpy(), 'components': comps.cpu().numpy(), 'explained_variance': lam[:2].copy(),
             'explained_variance_ratio': lam[:2] / trace, 'eigenvalues': lam, 'X': X, 'limits': tuple(lim[4:]), 'minmax': tuple(lim[:4]),
-            'sweeps': int(sweeps), 'offdiag': offdiag, 'n_rows': n, 'dim': d}
+            'sweeps': sweeps, 'offdiag': offdiag, 'n_rows': n, 'dim': d}
 
 
 def plot_rectangle(canvas):

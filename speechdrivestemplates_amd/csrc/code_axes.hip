@@ -2,34 +2,26 @@
 // along ALL of its principal axes, the populated range of every axis is measured by exact order statistics, and any point of that
 // space is mapped to the nearest row of the table.  The output file is what the two demo modes of the reference consume
 // (pose2pose.py:50-56 DEMO.CODE_PATH, voice2pose.py:107-117 DEMO.CODE_INDEX / CODE_INDEX_B).  Four stages:
-//   eigh      : the one-wave cyclic Jacobi of jacobi.h (shared with code_pca.hip), every component emitted.
+//   eigh      : the eigen kernel of code_pca.hip (the one-wave cyclic Jacobi of jacobi.h), asked for every component.
 //   project   : P (N, D) = (x - mean) . comps^T.  A tile of 32 rows is staged in LDS by coalesced fp32 loads and centred there;
 //               thread per (row, axis) pair, the pairs of a tile in the order of P, so the float64 stores are contiguous.
 //   quantiles : radix select on the order-preserving uint64 image of the float64 bits, 8 passes of 8 bits; 256-bin histograms per
 //               (axis, rank) with integer atomics, in LDS first; the surviving prefix and the remaining rank stay on the device.
 //   nearest   : tiles of 128 table rows staged in LDS, 8 queries per workgroup, a (d2, n) pair per thread and query, reduced by
 //               comparing d2 first and n second; one partial per (query tile, row chunk), then a final kernel over the partials.
-// Everything is float64 on values converted exactly from fp32, every operation rounded on its own; no floating-point atomics.
-#include "common.h"
+// Everything is float64 on values converted exactly from fp32, every operation rounded on its own (exact_f64.h); no floating-point atomics.
 #include "jacobi.h"
 
 namespace {
 
-using sdt_jacobi::add_rn;
-using sdt_jacobi::mul_rn;
-using sdt_jacobi::sub_rn;
+using sdt_exact::add_rn;
+using sdt_exact::kMaxD;
+using sdt_exact::mul_rn;
+using sdt_exact::sub_rn;
 
-constexpr int kMaxD = sdt_jacobi::kMaxD;
 constexpr int kThreads = 256;
 constexpr int64_t kMaxRows = (int64_t)1 << 30;
 constexpr int kMaxQueries = 65536, kMaxRanks = 16;
-
-// ---- eigen-decomposition -----------------------------------------------------------------------------------------------------------------
-__global__ void __launch_bounds__(kMaxD) sdt_code_axes_eigh_kernel(const double* __restrict__ cov, int D, int max_sweeps, double rel_tol,
-                                                                   double* __restrict__ evals, double* __restrict__ comps,
-                                                                   double* __restrict__ info, int32_t* __restrict__ err) {
-    sdt_jacobi::eigh_one_wave(cov, D, max_sweeps, rel_tol, D, evals, comps, info, err);
-}
 
 // ---- projection --------------------------------------------------------------------------------------------------------------------------
 constexpr int kProjRows = 32, kProjMaxGrid = 2048;
@@ -295,14 +287,6 @@ inline int64_t nearest_ws_bytes(int64_t N, int64_t Q) {
 
 inline bool sizes_ok(int64_t N, int D) { return N >= 2 && N <= kMaxRows && D >= 2 && D <= kMaxD; }
 
-#define SDT_CHECK_SUPPORTED(cond, msg)              \
-    do {                                            \
-        if (!(cond)) {                              \
-            sdt_set_error("%s: %s", __func__, msg); \
-            return SDT_ERR_UNSUPPORTED;             \
-        }                                           \
-    } while (0)
-
 }  // namespace
 
 extern "C" int sdt_code_axes_eigh(const double* cov, int dim, int max_sweeps, double rel_tol, double* evals, double* comps, double* info,
@@ -311,8 +295,7 @@ extern "C" int sdt_code_axes_eigh(const double* cov, int dim, int max_sweeps, do
     SDT_CHECK_SUPPORTED(dim >= 2 && dim <= kMaxD, "dim must lie in [2, 64]");
     SDT_CHECK_ARG(max_sweeps >= 0 && max_sweeps <= 1000, "max_sweeps must lie in [0, 1000]");
     SDT_CHECK_ARG(rel_tol >= 0.0, "rel_tol must not be negative");
-    hipLaunchKernelGGL(sdt_code_axes_eigh_kernel, dim3(1), dim3(kMaxD), 0, (hipStream_t)stream, cov, dim, max_sweeps, rel_tol, evals, comps,
-                       info, err);
+    sdt_jacobi::launch_eigh(cov, dim, max_sweeps, rel_tol, dim, evals, comps, info, err, stream);
     SDT_LAUNCH_CHECK();
     return SDT_OK;
 }

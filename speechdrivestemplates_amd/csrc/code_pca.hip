@@ -3,22 +3,25 @@
 // the table leaving the device.  Four stages, nine small kernels:
 //   moments : column sums (partials per workgroup, ordered final reduce) -> mean; centred products of 16-row tiles staged in LDS
 //             (partials per workgroup, ordered final reduce) -> covariance.  Fixed grid, no floating-point atomics: deterministic.
-//   eigh    : cyclic Jacobi on the D x D covariance in LDS, one wave; eigenvalues ranked, two components with the sign rule.
+//   eigh    : cyclic Jacobi on the D x D covariance in LDS, one wave (jacobi.h: the sweeps that fgd.hip runs too); eigenvalues ranked,
+//             the leading components with the sign rule.  The one kernel serves sdt_code_pca_eigh (two components) and
+//             sdt_code_axes_eigh (all of them, code_axes.hip).
 //   project : X = (x - mean) . comp^T, per-workgroup min / max, then one workgroup reduces them and derives the axis limits.
 //   raster  : uint32 counters per plot pixel (integer atomics: exact in any order), then counter -> colour table -> uint8 RGB.
-// Everything is float64 on values converted exactly from fp32.  The binning rounds every operation on its own (no FMA contraction):
+// Everything is float64 on values converted exactly from fp32.  The binning rounds every operation on its own (exact_f64.h):
 // the tests recompute it with numpy from the returned coordinates and expect the same bins.  Contract and numbers: DESIGN.md section 12.
-#include "common.h"
 #include "jacobi.h"
 
 namespace {
 
-using sdt_jacobi::add_rn;
-using sdt_jacobi::div_rn;
-using sdt_jacobi::mul_rn;
-using sdt_jacobi::sub_rn;
+using sdt_exact::add_rn;
+using sdt_exact::div_rn;
+using sdt_exact::kMaxD;
+using sdt_exact::kMaxTri;
+using sdt_exact::mul_rn;
+using sdt_exact::sub_rn;
+using sdt_exact::tri_entry;
 
-constexpr int kMaxD = 64, kMaxTri = kMaxD * (kMaxD + 1) / 2;  // 2080 upper-triangle entries at D = 64
 constexpr int kThreads = 256, kTileRows = 16, kMaxGrid = 256;
 constexpr int kTriPerThread = (kMaxTri + kThreads - 1) / kThreads;  // 9
 constexpr int64_t kMaxRows = (int64_t)1 << 30;
@@ -86,16 +89,6 @@ __global__ void __launch_bounds__(kMaxD) sdt_code_pca_mean_kernel(const double* 
     }
 }
 
-// entry e of the upper triangle, row-major: (0,0) (0,1) .. (0,D-1) (1,1) ..
-__device__ __forceinline__ void tri_entry(int e, int D, int& i, int& j) {
-    i = 0;
-    while (e >= D - i) {
-        e -= D - i;
-        ++i;
-    }
-    j = i + e;
-}
-
 // workgroup b takes the 16-row tiles b, b + G, ...: the centred rows go to LDS, thread t owns the triangle entries t, t + 256, ...
 // and adds (x[n,i] - mean[i]) * (x[n,j] - mean[j]) row by row.  prods[b*2080 + e].
 __global__ void __launch_bounds__(kThreads) sdt_code_pca_cov_kernel(const float* __restrict__ x, int64_t N, int D, const double* __restrict__ mean,
@@ -154,11 +147,11 @@ __global__ void __launch_bounds__(kThreads) sdt_code_pca_cov_final_kernel(const 
 }
 
 // ---- eigen-decomposition -----------------------------------------------------------------------------------------------------------------
-// One wave: the cyclic Jacobi, the ranking and the sign rule of jacobi.h (shared with code_axes.hip), two components kept.
-__global__ void __launch_bounds__(kMaxD) sdt_code_pca_eigh_kernel(const double* __restrict__ cov, int D, int max_sweeps, double rel_tol,
-                                                                  double* __restrict__ evals, double* __restrict__ comps,
-                                                                  double* __restrict__ info, int32_t* __restrict__ err) {
-    sdt_jacobi::eigh_one_wave(cov, D, max_sweeps, rel_tol, 2, evals, comps, info, err);
+// One wave: the cyclic Jacobi, the ranking and the sign rule of jacobi.h, the n_comps leading components kept.
+__global__ void __launch_bounds__(kMaxD) sdt_code_eigh_kernel(const double* __restrict__ cov, int D, int max_sweeps, double rel_tol, int n_comps,
+                                                              double* __restrict__ evals, double* __restrict__ comps,
+                                                              double* __restrict__ info, int32_t* __restrict__ err) {
+    sdt_jacobi::eigh_one_wave(cov, D, max_sweeps, rel_tol, n_comps, evals, comps, info, err);
 }
 
 // ---- projection --------------------------------------------------------------------------------------------------------------------------
@@ -312,6 +305,12 @@ inline int64_t ws_words(int64_t N) {
 
 }  // namespace
 
+void sdt_jacobi::launch_eigh(const double* cov, int dim, int max_sweeps, double rel_tol, int n_comps, double* evals, double* comps, double* info,
+                             int32_t* err, void* stream) {
+    hipLaunchKernelGGL(sdt_code_eigh_kernel, dim3(1), dim3(kMaxD), 0, (hipStream_t)stream, cov, dim, max_sweeps, rel_tol, n_comps, evals, comps,
+                       info, err);
+}
+
 extern "C" int64_t sdt_code_pca_workspace_bytes(int64_t n_rows, int dim) {
     if (n_rows < 2 || n_rows > kMaxRows || dim < 2 || dim > kMaxD) return 0;
     return ws_words(n_rows) * 8;
@@ -343,8 +342,7 @@ extern "C" int sdt_code_pca_eigh(const double* cov, int dim, int max_sweeps, dou
     SDT_CHECK_ARG(dim >= 2 && dim <= kMaxD, "dim must lie in [2, 64]");
     SDT_CHECK_ARG(max_sweeps >= 1 && max_sweeps <= 1000, "max_sweeps must lie in [1, 1000]");
     SDT_CHECK_ARG(rel_tol >= 0.0, "rel_tol must not be negative");
-    hipLaunchKernelGGL(sdt_code_pca_eigh_kernel, dim3(1), dim3(kMaxD), 0, (hipStream_t)stream, cov, dim, max_sweeps, rel_tol, evals, comps,
-                       info, err);
+    sdt_jacobi::launch_eigh(cov, dim, max_sweeps, rel_tol, 2, evals, comps, info, err, stream);
     SDT_LAUNCH_CHECK();
     return SDT_OK;
 }

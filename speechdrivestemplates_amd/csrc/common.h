@@ -22,6 +22,14 @@ void sdt_set_error(const char* fmt, ...);
         }                                                \
     } while (0)
 
+#define SDT_CHECK_SUPPORTED(cond, msg)                   \
+    do {                                                 \
+        if (!(cond)) {                                   \
+            sdt_set_error("%s: %s", __func__, msg);      \
+            return SDT_ERR_UNSUPPORTED;                  \
+        }                                                \
+    } while (0)
+
 #define SDT_LAUNCH_CHECK()                                                        \
     do {                                                                          \
         hipError_t e_ = hipGetLastError();                                        \

@@ -7,56 +7,34 @@
 //                different shifts: one per rank after an all-gather), takes the leading dim_used x dim_used block, and evaluates
 //                  FGD = |mean_A - mean_B|^2 + tr C_A + tr C_B - 2 sum_i sqrt(max(mu_i, 0)),  mu = eig(sym(S C_B S)),  S = C_A^(1/2)
 //                with two cyclic Jacobi decompositions in LDS (the eigenvalues of S C_B S are those of C_A C_B: the reference's
-//                tr sqrtm(C_A C_B) without a square root of a non-symmetric matrix).
-// Everything is float64 on values converted exactly from fp32, every operation of finalize rounded on its own (M2 and the products stay
-// exactly symmetric whichever lane computes an entry).  Contract and numbers: DESIGN.md section 13.
-#include "common.h"
+//                tr sqrtm(C_A C_B) without a square root of a non-symmetric matrix).  The sweeps are sdt_jacobi::sweep of jacobi.h, the
+//                routine the eigen kernel of code_pca.hip / code_axes.hip runs: there is no second copy.
+// Everything is float64 on values converted exactly from fp32, every operation of finalize rounded on its own (exact_f64.h; M2 and the
+// products stay exactly symmetric whichever lane computes an entry).  Contract and numbers: DESIGN.md section 13.
+#include "jacobi.h"
 
 namespace {
 
-constexpr int kMaxD = 64, kMaxTri = kMaxD * (kMaxD + 1) / 2;  // 2080 upper-triangle entries at dim = 64
+using sdt_exact::add_rn;
+using sdt_exact::div_rn;
+using sdt_exact::kLd;
+using sdt_exact::kMaxD;
+using sdt_exact::kMaxTri;
+using sdt_exact::mul_rn;
+using sdt_exact::ordered_sum;
+using sdt_exact::sub_rn;
+using sdt_exact::tri_entry;
+using sdt_exact::tri_index;
+using sdt_jacobi::trace_of;
+
 constexpr int kAccThreads = 256, kTileRows = 32;
 constexpr int kTriPerThread = (kMaxTri + kAccThreads - 1) / kAccThreads;  // 9
-constexpr int kLd = kMaxD + 1;  // pitch of the LDS matrices: a row read along the lanes and a column read along the lanes both spread over the banks
 constexpr int kMaxStates = 64;  // states per side of one finalize (one per rank)
 constexpr int64_t kMaxRows = (int64_t)1 << 30;
 
 // state, in 8-byte words: [0] rows (int64) | [1] 1 + first non-finite row, 0: none (int64) | shift (dim) | s1 (dim) | s2 (dim (dim+1) / 2)
 constexpr int kHdr = 2;
 inline int64_t state_words(int dim) { return kHdr + 2 * (int64_t)dim + (int64_t)dim * (dim + 1) / 2; }
-
-// float64 operations each rounded on its own (see speaker_stats.hip: HIP's own *_rn are plain operators under the default -ffp-contract)
-__device__ __forceinline__ double add_rn(double a, double b) {
-#pragma clang fp contract(off)
-    return a + b;
-}
-__device__ __forceinline__ double sub_rn(double a, double b) {
-#pragma clang fp contract(off)
-    return a - b;
-}
-__device__ __forceinline__ double mul_rn(double a, double b) {
-#pragma clang fp contract(off)
-    return a * b;
-}
-__device__ __forceinline__ double div_rn(double a, double b) {
-#pragma clang fp contract(off)
-    return a / b;
-}
-
-// entry e of the upper triangle, row-major: (0,0) (0,1) .. (0,D-1) (1,1) ..
-__device__ __forceinline__ void tri_entry(int e, int D, int& i, int& j) {
-    i = 0;
-    while (e >= D - i) {
-        e -= D - i;
-        ++i;
-    }
-    j = i + e;
-}
-// index of entry (i, j) of that triangle, any order of i and j
-__device__ __forceinline__ int tri_index(int i, int j, int D) {
-    const int a = i < j ? i : j, b = i < j ? j : i;
-    return a * D - a * (a - 1) / 2 + (b - a);
-}
 
 // ---- accumulate ------------------------------------------------------------------------------------------------------------------------
 // One workgroup.  Feature row r = x0[r, 0..d0) ++ x1[r, 0..d1).  Tiles of 32 rows go to LDS as x - shift; thread t owns the triangle
@@ -138,13 +116,6 @@ struct StateList {
     const double* b[kMaxStates];
 };
 
-// sum of red[0..D) in index order, the same value in every lane
-__device__ __forceinline__ double ordered_sum(const double* red, int D) {
-    double s = 0.0;
-    for (int i = 0; i < D; ++i) s = add_rn(s, red[i]);
-    return s;
-}
-
 // Lane k merges column k of the states p[0..ns) (dim x dim, leading D x D block): C[i*kLd + k] = covariance (ddof 1), mean[k].
 // -> rows; bad = 1 + the first non-finite row of the first state that recorded one.  C is left as M2 when rows < 2.
 __device__ long long merge_side(const double* const* p, int ns, int dim, int D, double* C, double* mean, long long& bad) {
@@ -198,94 +169,6 @@ __device__ long long merge_side(const double* const* p, int ns, int dim, int D, 
     return n;
 }
 
-// Cyclic Jacobi on the symmetric D x D matrix A (pitch kLd), one wave: lane k owns column k of A (kept whole: the mirror entries are written
-// back) and, with kVectors, column k of V^T (pitch kLd; Vt[k][:] = eigenvector of A[k][k] at the end).  Rutishauser's rotation zeroes A[p][q]:
-//   theta = (a_qq - a_pp) / (2 a_pq), t = sign(theta) / (|theta| + sqrt(theta^2 + 1)), c = 1 / sqrt(t^2 + 1), s = t c.
-// Before each sweep off = sqrt(sum of squared off-diagonal entries); stops at off <= rel_tol * ||A||_F (-> true) or after max_sweeps sweeps
-// (-> false; NaN never compares true, so a non-finite matrix ends this way).
-template <bool kVectors>
-__device__ bool jacobi(double* A, double* Vt, double* red, int D, int max_sweeps, double rel_tol, int& sweeps, double& off) {
-    const int k = threadIdx.x;
-    const bool active = k < D;
-    __syncthreads();
-    if (active) {
-        double s = 0.0;
-        for (int i = 0; i < D; ++i) {
-            s = add_rn(s, mul_rn(A[i * kLd + k], A[i * kLd + k]));
-            if (kVectors) Vt[i * kLd + k] = i == k ? 1.0 : 0.0;
-        }
-        red[k] = s;
-    }
-    __syncthreads();
-    const double tol = mul_rn(rel_tol, sqrt(ordered_sum(red, D)));
-    sweeps = 0;
-    for (;;) {
-        __syncthreads();
-        if (active) {
-            double s = 0.0;
-            for (int i = 0; i < D; ++i)
-                if (i != k) s = add_rn(s, mul_rn(A[i * kLd + k], A[i * kLd + k]));
-            red[k] = s;
-        }
-        __syncthreads();
-        off = sqrt(ordered_sum(red, D));
-        if (off <= tol) return true;
-        if (sweeps == max_sweeps) return false;
-        for (int p = 0; p < D - 1; ++p)
-            for (int q = p + 1; q < D; ++q) {
-                const double apq = A[p * kLd + q];  // the same address in every lane: a broadcast read
-                if (apq == 0.0) continue;            // (uniform)
-                const double app = A[p * kLd + p], aqq = A[q * kLd + q];
-                const double theta = div_rn(sub_rn(aqq, app), mul_rn(2.0, apq));
-                const double t = div_rn(copysign(1.0, theta), add_rn(fabs(theta), sqrt(add_rn(mul_rn(theta, theta), 1.0))));
-                const double c = div_rn(1.0, sqrt(add_rn(mul_rn(t, t), 1.0)));
-                const double s = mul_rn(t, c);
-                double akp = 0.0, akq = 0.0, vp = 0.0, vq = 0.0;
-                if (active) {
-                    akp = A[p * kLd + k];
-                    akq = A[q * kLd + k];
-                    if (kVectors) {
-                        vp = Vt[p * kLd + k];
-                        vq = Vt[q * kLd + k];
-                    }
-                }
-                __syncthreads();  // every lane has read a_pp, a_qq, a_pq before lanes p and q overwrite them
-                if (active) {
-                    if (k == p) {
-                        A[p * kLd + p] = sub_rn(app, mul_rn(t, apq));
-                        A[p * kLd + q] = 0.0;
-                    } else if (k == q) {
-                        A[q * kLd + q] = add_rn(aqq, mul_rn(t, apq));
-                        A[q * kLd + p] = 0.0;
-                    } else {
-                        const double np = sub_rn(mul_rn(c, akp), mul_rn(s, akq)), nq = add_rn(mul_rn(s, akp), mul_rn(c, akq));
-                        A[p * kLd + k] = np;
-                        A[q * kLd + k] = nq;
-                        A[k * kLd + p] = np;
-                        A[k * kLd + q] = nq;
-                    }
-                    if (kVectors) {
-                        Vt[p * kLd + k] = sub_rn(mul_rn(c, vp), mul_rn(s, vq));
-                        Vt[q * kLd + k] = add_rn(mul_rn(s, vp), mul_rn(c, vq));
-                    }
-                }
-                __syncthreads();
-            }
-        ++sweeps;
-    }
-}
-
-// trace of the D x D matrix M, diagonal added in index order; the same value in every lane
-__device__ __forceinline__ double trace_of(const double* M, double* red, int D) {
-    const int k = threadIdx.x;
-    __syncthreads();
-    if (k < D) red[k] = M[k * kLd + k];
-    __syncthreads();
-    const double s = ordered_sum(red, D);
-    __syncthreads();
-    return s;
-}
-
 // One wave, three LDS matrices (99 840 bytes of gfx950's 160 KB): P = C_A, then S, then sym(S C_B S); Q = C_B, then S C_B S; R = V^T, then C_B S.
 __global__ void __launch_bounds__(kMaxD) sdt_fgd_finalize_kernel(StateList st, int num_states, int dim, int D, int max_sweeps, double rel_tol,
                                                                  double* __restrict__ out, int32_t* __restrict__ err) {
@@ -303,6 +186,7 @@ __global__ void __launch_bounds__(kMaxD) sdt_fgd_finalize_kernel(StateList st, i
     if (n_a < 2 || n_b < 2) error |= 2;
     if (bad_a != 0 || bad_b != 0) error |= 4;
     double fgd = nan, gap2 = nan, tr_a = nan, tr_b = nan, tr_root = nan, off1 = nan, off2 = nan, min1 = nan, min2 = nan;
+    double frob;  // (of each decomposed matrix: not reported)
     int sweeps1 = 0, sweeps2 = 0;
     if (error == 0) {  // (uniform)
         if (active) red[k] = mul_rn(sub_rn(mean_a[k], mean_b[k]), sub_rn(mean_a[k], mean_b[k]));
@@ -311,7 +195,7 @@ __global__ void __launch_bounds__(kMaxD) sdt_fgd_finalize_kernel(StateList st, i
         tr_a = trace_of(P, red, D);
         tr_b = trace_of(Q, red, D);
         // C_A = V Lambda V^T
-        if (!jacobi<true>(P, R, red, D, max_sweeps, rel_tol, sweeps1, off1)) error |= 1;
+        if (!sdt_jacobi::sweep<true>(P, R, red, D, max_sweeps, rel_tol, sweeps1, off1, frob)) error |= 1;
         __syncthreads();
         if (active) red[k] = P[k * kLd + k];
         __syncthreads();
@@ -346,7 +230,7 @@ __global__ void __launch_bounds__(kMaxD) sdt_fgd_finalize_kernel(StateList st, i
         // sym(.) -> P
         if (active)
             for (int i = 0; i < D; ++i) P[i * kLd + k] = mul_rn(0.5, add_rn(Q[i * kLd + k], Q[k * kLd + i]));
-        if (!jacobi<false>(P, R, red, D, max_sweeps, rel_tol, sweeps2, off2)) error |= 1;
+        if (!sdt_jacobi::sweep<false>(P, R, red, D, max_sweeps, rel_tol, sweeps2, off2, frob)) error |= 1;  // (begins with a barrier)
         __syncthreads();
         if (active) red[k] = P[k * kLd + k];
         __syncthreads();

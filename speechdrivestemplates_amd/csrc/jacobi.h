@@ -1,76 +1,54 @@
-// Device code shared by code_pca.hip (two components, the epoch figure) and code_axes.hip (all components): float64 operations each
-// rounded on its own, and the one-wave cyclic Jacobi of a D x D covariance, 2 <= D <= 64, with the ranking and the sign rule.
-// Both kernels run the same statements, so the eigenpairs they have in common carry the same bits.
+// The one-wave cyclic Jacobi of a symmetric D x D float64 matrix in LDS, 2 <= D <= 64, every operation rounded on its own.  There is one
+// copy of the sweeps: the eigen kernel behind sdt_code_pca_eigh / sdt_code_axes_eigh (code_pca.hip; ranking and sign rule below) and both
+// decompositions of sdt_fgd_finalize (fgd.hip) run these statements, so equal matrices give equal bits whoever asks.
 #pragma once
-#include "common.h"
+#include "exact_f64.h"
 
 namespace sdt_jacobi {
 
-constexpr int kMaxD = 64;
-constexpr int kLd = kMaxD + 1;  // pitch of the Jacobi matrix in LDS: the mirror writes A[k][p] of 64 lanes fall on different banks
+using sdt_exact::add_rn;
+using sdt_exact::div_rn;
+using sdt_exact::kLd;
+using sdt_exact::kMaxD;
+using sdt_exact::mul_rn;
+using sdt_exact::ordered_sum;
+using sdt_exact::sub_rn;
 
-// float64 operations each rounded on its own (see speaker_stats.hip: HIP's own *_rn are plain operators under the default -ffp-contract)
-__device__ __forceinline__ double add_rn(double a, double b) {
-#pragma clang fp contract(off)
-    return a + b;
-}
-__device__ __forceinline__ double sub_rn(double a, double b) {
-#pragma clang fp contract(off)
-    return a - b;
-}
-__device__ __forceinline__ double mul_rn(double a, double b) {
-#pragma clang fp contract(off)
-    return a * b;
-}
-__device__ __forceinline__ double div_rn(double a, double b) {
-#pragma clang fp contract(off)
-    return a / b;
-}
-
-// sum of red[0..D) in index order, the same value in every lane
-__device__ __forceinline__ double ordered_sum(const double* red, int D) {
-    double s = 0.0;
-    for (int i = 0; i < D; ++i) s = add_rn(s, red[i]);
+// trace of the D x D matrix M (pitch kLd), diagonal added in index order; the same value in every lane
+__device__ __forceinline__ double trace_of(const double* M, double* red, int D) {
+    const int k = threadIdx.x;
+    __syncthreads();
+    if (k < D) red[k] = M[k * kLd + k];
+    __syncthreads();
+    const double s = ordered_sum(red, D);
+    __syncthreads();
     return s;
 }
 
-// One wave of kMaxD lanes (the whole workgroup).  Lane k owns column k of the symmetric matrix A (kept whole: rows p and q are read along
-// k, the mirror entries are written back) and column k of V^T.  Row-cyclic sweeps over the pairs p < q; a rotation (Rutishauser's
-// formulas) zeroes A[p][q]:
+// One wave of kMaxD lanes (the whole workgroup); A, Vt (both pitch kLd) and red (kMaxD) are the caller's, in LDS.  Lane k owns column k of
+// the symmetric matrix A (kept whole: rows p and q are read along k, the mirror entries are written back) and, with kVectors, column k of
+// V^T, which starts as the identity (Vt[k][:] = eigenvector of A[k][k] at the end).  Row-cyclic sweeps over the pairs p < q; a rotation
+// (Rutishauser's formulas) zeroes A[p][q]:
 //   theta = (a_qq - a_pp) / (2 a_pq), t = sign(theta) / (|theta| + sqrt(theta^2 + 1)), c = 1 / sqrt(t^2 + 1), s = t c.
-// Before each sweep: off = sqrt(sum of squared off-diagonal entries); stop when off <= rel_tol * ||C||_F, error bit 0 if max_sweeps
-// sweeps did not get there (NaN never compares true, so a non-finite matrix ends the same way); bit 1: trace(C) is not positive.
-// info = [sweeps done, final off, ||C||_F, trace(C)].  evals (D) are ranked in descending order (ties: the lower column first); the
-// n_comps leading eigenvectors go to comps (n_comps, D), each signed so that its entry of largest magnitude (first of equals) is positive.
-__device__ __forceinline__ void eigh_one_wave(const double* __restrict__ cov, int D, int max_sweeps, double rel_tol, int n_comps,
-                                              double* __restrict__ evals, double* __restrict__ comps, double* __restrict__ info,
-                                              int32_t* __restrict__ err) {
-    __shared__ double A[kMaxD * kLd];
-    __shared__ double Vt[kMaxD * kMaxD];
-    __shared__ double red[kMaxD];
+// Before each sweep off = sqrt(sum of squared off-diagonal entries); stops at off <= rel_tol * frob, frob = ||A||_F of the matrix given
+// (-> true), or after max_sweeps sweeps (-> false; NaN never compares true, so a non-finite matrix ends this way).
+template <bool kVectors>
+__device__ bool sweep(double* A, double* Vt, double* red, int D, int max_sweeps, double rel_tol, int& sweeps, double& off, double& frob) {
     const int k = threadIdx.x;
     const bool active = k < D;
-    if (active)
-        for (int i = 0; i < D; ++i) {
-            A[i * kLd + k] = cov[i * D + k];
-            Vt[i * kMaxD + k] = i == k ? 1.0 : 0.0;
-        }
-    __syncthreads();
+    __syncthreads();  // the caller's last write to A
     if (active) {
         double s = 0.0;
-        for (int i = 0; i < D; ++i) s = add_rn(s, mul_rn(A[i * kLd + k], A[i * kLd + k]));
+        for (int i = 0; i < D; ++i) {
+            s = add_rn(s, mul_rn(A[i * kLd + k], A[i * kLd + k]));
+            if (kVectors) Vt[i * kLd + k] = i == k ? 1.0 : 0.0;
+        }
         red[k] = s;
     }
     __syncthreads();
-    const double frob = sqrt(ordered_sum(red, D));
-    __syncthreads();
-    if (active) red[k] = A[k * kLd + k];
-    __syncthreads();
-    const double trace = ordered_sum(red, D);
+    frob = sqrt(ordered_sum(red, D));
     const double tol = mul_rn(rel_tol, frob);
-
-    int sweeps = 0, error = 0;
-    double off = 0.0;
+    sweeps = 0;
     for (;;) {
         __syncthreads();
         if (active) {
@@ -81,11 +59,8 @@ __device__ __forceinline__ void eigh_one_wave(const double* __restrict__ cov, in
         }
         __syncthreads();
         off = sqrt(ordered_sum(red, D));
-        if (off <= tol) break;
-        if (sweeps == max_sweeps) {
-            error |= 1;
-            break;
-        }
+        if (off <= tol) return true;
+        if (sweeps == max_sweeps) return false;
         for (int p = 0; p < D - 1; ++p)
             for (int q = p + 1; q < D; ++q) {
                 const double apq = A[p * kLd + q];  // the same address in every lane: a broadcast read
@@ -99,8 +74,10 @@ __device__ __forceinline__ void eigh_one_wave(const double* __restrict__ cov, in
                 if (active) {
                     akp = A[p * kLd + k];
                     akq = A[q * kLd + k];
-                    vp = Vt[p * kMaxD + k];
-                    vq = Vt[q * kMaxD + k];
+                    if (kVectors) {
+                        vp = Vt[p * kLd + k];
+                        vq = Vt[q * kLd + k];
+                    }
                 }
                 __syncthreads();  // every lane has read a_pp, a_qq, a_pq before lanes p and q overwrite them
                 if (active) {
@@ -117,13 +94,35 @@ __device__ __forceinline__ void eigh_one_wave(const double* __restrict__ cov, in
                         A[k * kLd + p] = np;
                         A[k * kLd + q] = nq;
                     }
-                    Vt[p * kMaxD + k] = sub_rn(mul_rn(c, vp), mul_rn(s, vq));
-                    Vt[q * kMaxD + k] = add_rn(mul_rn(s, vp), mul_rn(c, vq));
+                    if (kVectors) {
+                        Vt[p * kLd + k] = sub_rn(mul_rn(c, vp), mul_rn(s, vq));
+                        Vt[q * kLd + k] = add_rn(mul_rn(s, vp), mul_rn(c, vq));
+                    }
                 }
                 __syncthreads();
             }
         ++sweeps;
     }
+}
+
+// The eigen-decomposition of the covariance cov (D, D): load, trace, sweep, then the ranking and the sign rule.  Error bit 0: max_sweeps
+// sweeps did not converge; bit 1: trace(C) is not positive.  info = [sweeps done, final off, ||C||_F, trace(C)].  evals (D) are ranked in
+// descending order (ties: the lower column first); the n_comps leading eigenvectors go to comps (n_comps, D), each signed so that its entry
+// of largest magnitude (first of equals) is positive.
+__device__ __forceinline__ void eigh_one_wave(const double* __restrict__ cov, int D, int max_sweeps, double rel_tol, int n_comps,
+                                              double* __restrict__ evals, double* __restrict__ comps, double* __restrict__ info,
+                                              int32_t* __restrict__ err) {
+    __shared__ double A[kMaxD * kLd];
+    __shared__ double Vt[kMaxD * kLd];
+    __shared__ double red[kMaxD];
+    const int k = threadIdx.x;
+    const bool active = k < D;
+    if (active)
+        for (int i = 0; i < D; ++i) A[i * kLd + k] = cov[i * D + k];
+    const double trace = trace_of(A, red, D);
+    int sweeps;
+    double off, frob;
+    int error = sweep<true>(A, Vt, red, D, max_sweeps, rel_tol, sweeps, off, frob) ? 0 : 1;
     if (!(trace > 0.0)) error |= 2;
 
     // rank of eigenvalue k in descending order (ties: the lower index first)
@@ -142,13 +141,13 @@ __device__ __forceinline__ void eigh_one_wave(const double* __restrict__ cov, in
         if (rank < n_comps) {  // eigenvector k = row k of V^T; its entry of largest magnitude (first of equals) is made positive
             double big = -1.0, sign = 1.0;
             for (int i = 0; i < D; ++i) {
-                const double v = Vt[k * kMaxD + i];
+                const double v = Vt[k * kLd + i];
                 if (fabs(v) > big) {
                     big = fabs(v);
                     sign = v < 0.0 ? -1.0 : 1.0;
                 }
             }
-            for (int i = 0; i < D; ++i) comps[rank * D + i] = mul_rn(sign, Vt[k * kMaxD + i]);
+            for (int i = 0; i < D; ++i) comps[rank * D + i] = mul_rn(sign, Vt[k * kLd + i]);
         }
     }
     if (k == 0) {
@@ -159,5 +158,9 @@ __device__ __forceinline__ void eigh_one_wave(const double* __restrict__ cov, in
         err[0] = error;
     }
 }
+
+// the one eigen kernel's launcher (code_pca.hip); the two entry points validate their own arguments first and check the launch after
+void launch_eigh(const double* cov, int dim, int max_sweeps, double rel_tol, int n_comps, double* evals, double* comps, double* info,
+                 int32_t* err, void* stream);
 
 }  // namespace sdt_jacobi

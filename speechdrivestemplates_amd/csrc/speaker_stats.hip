@@ -4,10 +4,15 @@
 // lives in a float64 buffer between windows.  sdt_speaker_stats_final_kernel averages the per-chunk tables over chunks, then
 // over frames, in index order (np.average(axis=0) twice), drops the 16 keypoints 4_2 deletes and reports counts and flags.
 // Root deduction and the detection test run in the file's element type; everything after it is float64 with every operation
-// rounded on its own (no FMA contraction), so the results are the reference's bits.  Contract and numbers: DESIGN.md section 11.
-#include "common.h"
+// rounded on its own (exact_f64.h: no FMA contraction), so the results are the reference's bits.  Contract and numbers: DESIGN.md section 11.
+#include "exact_f64.h"
 
 namespace {
+
+using sdt_exact::add_rn;
+using sdt_exact::div_rn;
+using sdt_exact::mul_rn;
+using sdt_exact::sub_rn;
 
 constexpr int kKp = 137, kThreads = 256, kFinalThreads = 64, kMaxFrames = 2048;
 constexpr int kFields = 7;  // parted n, x, y | global n, x, y | first non-finite row + 1 (0: none)
@@ -24,25 +29,6 @@ __device__ __forceinline__ int part_root(int k) {
 __device__ __forceinline__ int kept_index(int k) {
     if (k == 1 || (k >= 8 && k <= 14) || (k >= 17 && k <= 24)) return -1;
     return k - (k > 1) - min(max(k - 8, 0), 7) - min(max(k - 17, 0), 8);
-}
-
-// float64 operations each rounded on its own.  HIP's mul_rn / add_rn are plain operators compiled under the default
-// -ffp-contract, so x*w + om*q made of them still becomes an FMA; these carry the pragma in their own bodies.
-__device__ __forceinline__ double add_rn(double a, double b) {
-#pragma clang fp contract(off)
-    return a + b;
-}
-__device__ __forceinline__ double sub_rn(double a, double b) {
-#pragma clang fp contract(off)
-    return a - b;
-}
-__device__ __forceinline__ double mul_rn(double a, double b) {
-#pragma clang fp contract(off)
-    return a * b;
-}
-__device__ __forceinline__ double div_rn(double a, double b) {
-#pragma clang fp contract(off)
-    return a / b;
 }
 
 template <typename T>
