@@ -549,6 +549,49 @@ int sdt_code_axes_nearest(const float* x, int64_t n_rows, int dim, const double*
                           int64_t* first_bad_query, void* workspace, int64_t workspace_bytes, void* stream);
 
 /*
+ * Clusters of the template-code table and the row that stands for each (code_clusters.py; DESIGN.md section 19 is the contract): k-means
+ * on the (n_rows, dim) fp32 table x, so that a user can name DEMO.CODE_INDEX / CODE_INDEX_B (voice2pose.py:107-117) and write a
+ * DEMO.CODE_PATH file with one code per cluster (pose2pose.py:50-56).  Supported sizes: 2 <= n_rows <= 2^24, 2 <= dim <= 64, 1 <= k <= 64,
+ * k <= n_rows; outside them the workspace queries return 0 and the entry points SDT_ERR_UNSUPPORTED.  All arithmetic is float64 on values
+ * converted exactly from fp32, every operation rounded on its own; d2(a, b) = sum over d ascending of (a[d] - b[d])^2.  Rows form chunks
+ * of 1024 consecutive rows; every sum over rows runs rows ascending inside a chunk from +0.0, then chunks ascending.  No floating-point
+ * atomics, no allocation, no workspace read before it is written; every pointer is a device buffer; row and cluster numbers read from
+ * device buffers are checked against the sizes given.  The table must be finite (sdt_code_pca_moments reports the first row that is not).
+ *   seed_update: m[n] = d2(x[n], x[seeds[j]]) if first != 0, else min(m[n], that); leaves in the workspace, per chunk, the ordered sum of
+ *     m, the largest m with its lowest row, and the last row with m > 0.  0 <= j < 64.
+ *   seed_pick (after seed_update, same workspace) writes seeds[j], 1 <= j < min(64, n_rows).  mode 0, k-means++ with 0 <= u <= 1: P[c] =
+ *     running sum of the chunk sums, T = P[last], r = u T; the chunk is the first with P[c] > r; inside it the running sum starts at
+ *     P[c - 1] (0 for c = 0) and adds m[n] ascending; the seed is the first row whose running sum exceeds r, else the chunk's last row
+ *     with m > 0; no chunk passes: the table's last row with m > 0; T == 0: the lowest row not among seeds[0, j).  mode 1, farthest: the
+ *     row of the largest m, of equals the lowest; a largest m of 0: the T == 0 rule.  info (4 float64): T (mode 1: the largest m), r, the
+ *     chunk or -1, the rule that chose (0 the walk, 1 the chunk's last positive row, 2 the table's, 3 T == 0, 4 farthest).
+ *   assign: labels[n] = argmin over c of d2(x[n], centers[c]), of equals the lowest c; changed[0] = the number of rows whose label differs
+ *     from the one labels held before (first != 0: labels is not read and every row counts).  centers is (k, dim) float64.
+ *   update: total[c][d] = the ordered sum of x[n, d] over the rows with labels[n] == c, counts[c] = their number (int32),
+ *     centers[c][d] = total / (double)count; a cluster without rows keeps its centre.  Workspace:
+ *     sdt_code_clusters_update_workspace_bytes(n_rows, dim, k) bytes (chunks * k * dim float64 partials and the chunk counts).
+ *   final: assigns against centers once more, then numbers the clusters by descending count (ties: the lower number first) and writes, in
+ *     that numbering, labels (n_rows int32), centers_out (k, dim; must not be centers), counts (k int32), within_ss (k) = the ordered sum
+ *     of d2 over the members, code_index (k int64) = the member with the smallest (d2, row) and code_dist2 (k) its d2 (-1 and +inf for a
+ *     cluster without rows), order (k int32) = the old number of every new cluster, inertia[0] = the ascending sum of within_ss.
+ *     Workspace: sdt_code_clusters_final_workspace_bytes(n_rows, dim, k) bytes.
+ */
+int64_t sdt_code_clusters_seed_workspace_bytes(int64_t n_rows, int dim);
+int sdt_code_clusters_seed_update(const float* x, int64_t n_rows, int dim, const int64_t* seeds, int j, int first, double* m, void* workspace,
+                                  int64_t workspace_bytes, void* stream);
+int sdt_code_clusters_seed_pick(const double* m, int64_t n_rows, int mode, double u, int64_t* seeds, int j, double* info, void* workspace,
+                                int64_t workspace_bytes, void* stream);
+int sdt_code_clusters_assign(const float* x, int64_t n_rows, int dim, const double* centers, int k, int32_t* labels, int first, int64_t* changed,
+                             void* stream);
+int64_t sdt_code_clusters_update_workspace_bytes(int64_t n_rows, int dim, int k);
+int sdt_code_clusters_update(const float* x, int64_t n_rows, int dim, const int32_t* labels, int k, double* centers, int32_t* counts,
+                             void* workspace, int64_t workspace_bytes, void* stream);
+int64_t sdt_code_clusters_final_workspace_bytes(int64_t n_rows, int dim, int k);
+int sdt_code_clusters_final(const float* x, int64_t n_rows, int dim, const double* centers, int k, int32_t* labels, double* centers_out,
+                            int32_t* counts, double* within_ss, double* inertia, int64_t* code_index, double* code_dist2, int32_t* order,
+                            void* workspace, int64_t workspace_bytes, void* stream);
+
+/*
  * The epoch-level validation metric, the Frechet gesture distance (core/utils/fgd.py:6-64, called from voice2pose.py:432-446; DESIGN.md
  * section 13 is the contract).  A feature row is row r of the fp32 (rows, d0) tensor x0 followed by row r of the fp32 (rows, d1) tensor
  * x1 (x1 NULL with d1 = 0); dim = d0 + d1, 2 <= dim <= 64.  All arithmetic is float64.  No allocation; every pointer except the two

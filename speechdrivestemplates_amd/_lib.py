@@ -136,6 +136,14 @@ SIGNATURES = {
     "sdt_code_axes_quantiles": [_p, _i64, _i, _p, _i, _p, _p, _i64, _p],
     "sdt_code_axes_nearest_workspace_bytes": [_i64, _i, _i64],  # (returns int64_t: restype set in load())
     "sdt_code_axes_nearest": [_p, _i64, _i, _p, _i64, _p, _p, _p, _p, _i64, _p],
+    "sdt_code_clusters_seed_workspace_bytes": [_i64, _i],  # (returns int64_t: restype set in load())
+    "sdt_code_clusters_seed_update": [_p, _i64, _i, _p, _i, _i, _p, _p, _i64, _p],
+    "sdt_code_clusters_seed_pick": [_p, _i64, _i, C.c_double, _p, _i, _p, _p, _i64, _p],
+    "sdt_code_clusters_assign": [_p, _i64, _i, _p, _i, _p, _i, _p, _p],
+    "sdt_code_clusters_update_workspace_bytes": [_i64, _i, _i],  # (returns int64_t: restype set in load())
+    "sdt_code_clusters_update": [_p, _i64, _i, _p, _i, _p, _p, _p, _i64, _p],
+    "sdt_code_clusters_final_workspace_bytes": [_i64, _i, _i],  # (returns int64_t: restype set in load())
+    "sdt_code_clusters_final": [_p, _i64, _i, _p, _i, _p, _p, _p, _p, _p, _p, _p, _p, _p, _i64, _p],
     "sdt_fgd_state_bytes": [_i],  # (returns int64_t: restype set in load())
     "sdt_fgd_accumulate": [_p, _i, _p, _i, _i64, _p, _i64, _i64, _p],
     "sdt_fgd_finalize": [C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), _i, _i, _i, _i, C.c_double, _p, _p, _p],
@@ -209,6 +217,9 @@ def load():
     lib.sdt_code_pca_workspace_bytes.restype = C.c_int64
     lib.sdt_code_axes_quantiles_workspace_bytes.restype = C.c_int64
     lib.sdt_code_axes_nearest_workspace_bytes.restype = C.c_int64
+    lib.sdt_code_clusters_seed_workspace_bytes.restype = C.c_int64
+    lib.sdt_code_clusters_update_workspace_bytes.restype = C.c_int64
+    lib.sdt_code_clusters_final_workspace_bytes.restype = C.c_int64
     lib.sdt_fgd_state_bytes.restype = C.c_int64
     lib.sdt_jpeg_workspace_bytes.restype = C.c_int64
     lib.sdt_jpeg_intervals.restype = C.c_int64
