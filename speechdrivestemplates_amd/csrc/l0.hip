@@ -57,26 +57,37 @@ struct L0Window {
 };
 
 // grid (chunks, B); mom[b][54] doubles (zeroed by the caller)
+// FEW (an image of at most L0_FEW pixels): sums and products in fp64, where the product of two fp32 values is exact.  The variance of a channel
+// is a quadratic form of these moments minus m^2, and with fp32 products it carries 2^-24 (1 + (mean/std)^2) of relative error; among the 64
+// channels of a two-pixel image some have their two outputs close together (mean/std of 100 .. 200: the forward output lost two digits, 2.9e-4
+// of max at (B, H, W) = (2, 1, 2)) -- the case colstats_kernel (norm.hip) meets with up to four rows, with the same remedy and the same
+// threshold.  A separate instantiation: the 54 fp64 accumulators would otherwise count against every launch's registers; larger images keep
+// the fp32 partials and their bits.
+#define L0_FEW 4
+template <bool FEW> struct L0MomAcc { typedef float type; };
+template <> struct L0MomAcc<true> { typedef double type; };
+template <bool FEW>
 __global__ __launch_bounds__(256) void l0_moments_kernel(const float* __restrict__ mel, double* __restrict__ mom, int H, int W,
                                                          int pix_per_block) {
+    typedef typename L0MomAcc<FEW>::type acc_t;
     __shared__ double sM[L0_NMOM];
     const int b = blockIdx.y, tid = threadIdx.x;
     if (tid < L0_NMOM) sM[tid] = 0.0;
     __syncthreads();
     const float* img = mel + (size_t)b * H * W;
     const int p0 = blockIdx.x * pix_per_block, p1 = min(H * W, p0 + pix_per_block);
-    float acc[L0_NMOM];
+    acc_t acc[L0_NMOM];
 #pragma unroll
-    for (int i = 0; i < L0_NMOM; ++i) acc[i] = 0.f;
+    for (int i = 0; i < L0_NMOM; ++i) acc[i] = (acc_t)0;
     for (int p = p0 + tid; p < p1; p += 256) {
         float nb[L0_T];
         l0_gather(img, H, W, p / W, p % W, nb);
         int k = L0_T;
 #pragma unroll
         for (int t = 0; t < L0_T; ++t) {
-            acc[t] += nb[t];
+            acc[t] += (acc_t)nb[t];
 #pragma unroll
-            for (int u = t; u < L0_T; ++u) acc[k++] += nb[t] * nb[u];
+            for (int u = t; u < L0_T; ++u) acc[k++] += (acc_t)nb[t] * (acc_t)nb[u];
         }
     }
 #pragma unroll
@@ -418,7 +429,10 @@ extern "C" int sdt_l0_block_fwd_t(const float* mel, const float* w, void* z, int
     hipStream_t s = (hipStream_t)stream;
     const int HW = H * W, ppb = l0_ppb(HW);
     dim3 grid(cdiv(HW, ppb), B);
-    hipLaunchKernelGGL(l0_moments_kernel, grid, dim3(256), 0, s, mel, mom, H, W, ppb);
+    if (HW <= L0_FEW)
+        hipLaunchKernelGGL(l0_moments_kernel<true>, grid, dim3(256), 0, s, mel, mom, H, W, ppb);
+    else
+        hipLaunchKernelGGL(l0_moments_kernel<false>, grid, dim3(256), 0, s, mel, mom, H, W, ppb);
     const double n = groups == 1 ? (double)B * HW : (double)HW;
     hipLaunchKernelGGL(l0_finalize_kernel, dim3(cdiv(groups * L0_C, 64)), dim3(64), 0, s, mom, w, mean, rstd, running_mean,
                        running_var, num_batches_tracked, B, groups, n, eps, momentum);

@@ -4,7 +4,8 @@ copies live in HBM as bf16, products run on v_mfma_f32_32x32x16_bf16, accumulati
 The reference has no bf16 mode, so the tolerances are STATED here, per layer of the comparison:
   * one kernel against float64 on the SAME bf16-rounded operands: the products are exact in fp32, so what remains is the fp32 accumulation
     (1e-5 of max on the fp32 outputs: weight gradient, statistics) and ONE rounding of the output to bf16 (2^-8 = 3.9e-3 of each element's
-    magnitude -> 5e-3 of max);
+    magnitude -> 5e-3 of max).  That bar is the only one in THIS file; the norm and first-block kernels are held per element to half a bf16
+    step, and bit for bit to their fp32-store instantiations, at the edge shapes of tests/test_edge_shapes_bf16_gpu.py;
   * the bf16 chain / train step against the fp32 one and against the float64 oracle: prediction 4e-2 of max, losses 2e-2, every gradient
     tensor with cosine similarity >= 0.97 to the float64 gradient and within 40 % of its max-norm.  (The round-3 mode that only rounded the
     conv OPERANDS met 25 %; storing y, z, dz and dy of seven blocks as bf16 as well puts the two deepest tensors of the backward chain -- the

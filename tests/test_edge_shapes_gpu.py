@@ -585,8 +585,10 @@ def bn_eval(y, gamma, beta, rm, rv):
 
 
 @functools.lru_cache(maxsize=None)
-def colnorm_data(kind, C, R, rho=None, margin=KINK):
-    """Inputs of one column-norm case (float64, fp32-representable, clear of the kink).  ``rho``: per-channel mean = rho x std."""
+def colnorm_data(kind, C, R, rho=None, margin=KINK, rnd=f32, off_kink=_off_kink):
+    """Inputs of one column-norm case (float64, fp32-representable, clear of the kink).  ``rho``: per-channel mean = rho x std.
+    ``rnd`` / ``off_kink``: the rounding of y and dz (the affine parameters stay fp32) and the matching way off the kink (test_edge_shapes_bf16_gpu.py: bf16-representable
+    inputs, moved by whole bf16 steps)."""
     G = 1 if kind == "BN" else (3 if rho is None else 2)
     g = torch.Generator().manual_seed(7 * C + R + (0 if kind == "IN" else 100000) + (0 if rho is None else 1000 * int(rho) + 17))
     y = torch.randn(G, R, C, generator=g, dtype=torch.float64)
@@ -595,8 +597,8 @@ def colnorm_data(kind, C, R, rho=None, margin=KINK):
     else:
         sd = 0.5 + torch.rand(C, generator=g, dtype=torch.float64) * 2.0
         y = (y + rho) * sd
-    y = f32(y)
-    gz = f32(torch.randn(G, R, C, generator=g, dtype=torch.float64))
+    y = rnd(y)
+    gz = rnd(torch.randn(G, R, C, generator=g, dtype=torch.float64))
     d = {"y": y, "gz": gz, "G": G}
     if kind == "BN":
         d["gamma"] = f32(1 + 0.1 * torch.randn(C, generator=g, dtype=torch.float64))
@@ -610,7 +612,7 @@ def colnorm_data(kind, C, R, rho=None, margin=KINK):
     else:
         def pre(yy):
             return (in_pre(yy),)
-    d["y"] = _off_kink(y, pre, margin, spread=None if rho is None else 2.5)
+    d["y"] = off_kink(y, pre, margin, spread=None if rho is None else 2.5)
     return d
 
 
