@@ -752,6 +752,32 @@ int sdt_adam_step_guarded_f32(float* p, const float* g, float* m, float* v, int6
                               float eps, float weight_decay, const void* guard, float* ema, float ema_decay, void* state_dev,
                               void* stream);
 
+/*
+ * Per-tensor histograms and moments of a flat fp32 buffer, one segmented pass (tensor_hist.py; DESIGN.md section 20 is the contract;
+ * no counterpart in the reference, which calls SummaryWriter.add_histogram per parameter).  A segment is {offset, numel} in elements of
+ * flat[0..n): offset a multiple of 4, offset + numel <= n (else SDT_ERR_ARG).  Supported sizes: 1 <= n_segments <= 65536
+ * (sdt_tensor_hist_max_segments), numel < 2^32 per segment, at most 2^24 chunks of sdt_tensor_hist_chunk() elements in all; outside them
+ * both entry points return SDT_ERR_UNSUPPORTED.  Elements outside every segment are never read into a result.
+ *   plan (host only, no GPU): segments = HOST (n_segments, 2) int64 -> seg_plan HOST (n_segments, 3) {offset, numel, first chunk},
+ *     chunk_plan HOST (chunk_rows, 2) {segment, chunk number}, *n_chunks = rows used.  seg_plan / chunk_plan may be NULL (size query).
+ *   f32: seg_plan, chunk_plan = DEVICE copies of the plan; every row is checked again on the device against n_segments, n and n_chunks.
+ *     edges = DEVICE n_edges = 1549 ascending float64 bucket edges (edges[774] == 0).  Every element is v = (float)(x * scale), widened
+ *     to float64.  Zeroes and fills counts (n_segments, 1548) int64: bucket i = [edges[i], edges[i + 1]) by float64 compares, finite
+ *     values beyond the table in the outermost bucket of their sign; tallies (n_segments, 3) int64 {finite, NaN, +-inf}; stats
+ *     (n_segments, 4) float64 {min, max, sum, sum of squares} over the finite elements (none: +inf, -inf, +0, +0).  The sums have one
+ *     fixed order (csrc/tensor_hist.hip states it; tensor_hist.model_histograms is the same order in numpy, bit for bit); the integer
+ *     results use integer atomics and are exact.  partials: 4 * n_chunks doubles, contents irrelevant.  flat 16-byte aligned.
+ */
+int64_t sdt_tensor_hist_threads(void);
+int64_t sdt_tensor_hist_chunk(void);
+int64_t sdt_tensor_hist_buckets(void);
+int64_t sdt_tensor_hist_max_segments(void);
+int sdt_tensor_hist_plan(const int64_t* segments, int n_segments, int64_t n, int64_t* seg_plan, int64_t* chunk_plan, int64_t chunk_rows,
+                         int64_t* n_chunks);
+int sdt_tensor_hist_f32(const float* flat, int64_t n, const int64_t* seg_plan, int n_segments, const int64_t* chunk_plan, int64_t n_chunks,
+                        const double* edges, int n_edges, float scale, int64_t* counts, int64_t* tallies, double* stats, double* partials,
+                        void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -171,6 +171,12 @@ SIGNATURES = {
     "sdt_grad_sumsq_f64": [_p, _i64, _p, _p],
     "sdt_optim_guard_prep": [C.POINTER(C.c_void_p), _i, _f, C.c_double, _i, _p, _p],
     "sdt_adam_step_guarded_f32": [_p, _p, _p, _p, _i64, _p, _f, _f, _f, _f, _p, _p, _f, _p, _p],
+    "sdt_tensor_hist_threads": [],  # (the four getters return int64_t: restype set in load())
+    "sdt_tensor_hist_chunk": [],
+    "sdt_tensor_hist_buckets": [],
+    "sdt_tensor_hist_max_segments": [],
+    "sdt_tensor_hist_plan": [_p, _i, _i64, _p, _p, _i64, _p],
+    "sdt_tensor_hist_f32": [_p, _i64, _p, _i, _p, _i64, _p, _i, _f, _p, _p, _p, _p, _p],
 }
 F32, BF16 = 0, 1  # enum sdt_dtype
 
@@ -229,6 +235,8 @@ def load():
     lib.sdt_clip_resample_lds_bytes.restype = C.c_int64
     lib.sdt_grad_sumsq_partials.restype = C.c_int64
     lib.sdt_optim_guard_pass_elems.restype = C.c_int64
+    for name in ("threads", "chunk", "buckets", "max_segments"):
+        getattr(lib, "sdt_tensor_hist_" + name).restype = C.c_int64
     lib.sdt_conv_dw_group_plan_bytes.argtypes = [_i]
     lib.sdt_conv_dw_group_plan_bytes.restype = C.c_int64
     lib.sdt_conv_dw_workspace_bytes.argtypes = [_G]

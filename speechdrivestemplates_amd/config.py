@@ -82,6 +82,12 @@ _DEFAULTS = {
             # train/<figure> (with EPOCH_FIGURES), val/<metric>, test/<metric>, and, with the 'tensorboard' token of VIDEO_FORMAT, the sample
             # videos as animated GIFs that device frames get from the GPU encoder (gif.py, csrc/gif.hip).  False = no event file.
             "TENSORBOARD": False,
+            # HISTOGRAM_INTERVAL N (a positive integer; needs TENSORBOARD) = at every train step with global_step % N == 0 the master process
+            # adds, for every parameter an optimiser owns, the histograms weights/<name> and grads/<name> (the gradient Adam consumes, before
+            # clipping; ema/<name> too with TRAIN.EMA_DECAY), the scalars weight_norm/<name> and grad_norm/<name>, and nonfinite/<name> when a
+            # NaN or inf sits in that tensor.  One segmented GPU pass per optimiser buffer (tensor_hist.py, csrc/tensor_hist.hip; DESIGN.md
+            # section 20), taken after the step, outside any captured graph.  None = nothing is launched, the loop as it was.
+            "HISTOGRAM_INTERVAL": None,
             # CONV_F32_SPLIT (fp32 tensors): Conv2d products as six bf16 MFMA products of an exact three-way bf16 split of both operands, fp32
             # accumulation (csrc/convbf.hip; fp32-grade results, 1.3x faster); False = the fp32-MFMA kernels of rounds 3-4
             "CONV_F32_SPLIT": True,
@@ -167,6 +173,17 @@ def check_optim_guard(cfg, checkpoint_has_ema=False):
     if cfg.SYS.EVAL_WITH_EMA and decay is None and not checkpoint_has_ema:
         raise ValueError("SYS.EVAL_WITH_EMA needs an EMA to evaluate: set TRAIN.EMA_DECAY, or load a checkpoint that carries "
                          "'model_ema_state_dict' (one written by a run with TRAIN.EMA_DECAY)")
+
+
+def check_histograms(cfg):
+    """Validate SYS.HISTOGRAM_INTERVAL: None or a positive integer, and then SYS.TENSORBOARD must be set (there is nowhere else to write)."""
+    n = getattr(cfg.SYS, 'HISTOGRAM_INTERVAL', None)
+    if n is None:
+        return
+    if isinstance(n, bool) or not isinstance(n, int) or n < 1:
+        raise ValueError("SYS.HISTOGRAM_INTERVAL must be None or a positive integer, got %r" % (n,))
+    if not getattr(cfg.SYS, 'TENSORBOARD', False):
+        raise ValueError("SYS.HISTOGRAM_INTERVAL needs SYS.TENSORBOARD: the histograms go to the TensorBoard event file")
 
 
 def get_cfg_defaults():

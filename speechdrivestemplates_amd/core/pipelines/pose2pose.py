@@ -109,6 +109,7 @@ class Pose2Pose(Trainer):
         video_step = (self.rendering() and self.cfg.TRAIN.SAVE_VIDEO and self.is_master_process() and self.base_path is not None
                       and t_step % self.result_saving_interval_train == 0)
         losses, results = self.graphed_or_eager_step(batch, eager_ok=not video_step)
+        self.write_histograms(global_step)  # (SYS.HISTOGRAM_INTERVAL: after the step, outside the captured graph)
         self.last_losses = losses
         if t_step % self.cfg.SYS.LOG_INTERVAL == 0:
             if self.cfg.SYS.DISTRIBUTED:

@@ -41,6 +41,8 @@ class Trainer(object):
         if not torch.cuda.is_available():
             raise RuntimeError('this engine needs an AMD GPU (no CPU fallback); torch.cuda.is_available() is False')
         torch.cuda.set_device(int(os.environ.get('LOCAL_RANK', self.get_rank() % max(1, torch.cuda.device_count()))))
+        from ...config import check_histograms
+        check_histograms(cfg)  # SYS.HISTOGRAM_INTERVAL without SYS.TENSORBOARD: there is nowhere to write
 
     # -- process-group helpers (trainer.py:29-45) ---------------------------------------------------------
     def get_rank(self):
@@ -196,10 +198,15 @@ class Trainer(object):
         for opt in opts:
             opt.step()
 
+    def _owned_params(self, ema_only=False):
+        """[(state_dict key, optimiser, index)] of every parameter an optimiser owns (``ema_only``: that has an EMA)"""
+        owner = {id(p): (opt, i) for opt in self.optimizers.values() if opt.ema is not None or not ema_only
+                 for i, p in enumerate(opt.params)}
+        return [(name,) + owner[id(p)] for name, p in self.model.named_parameters() if id(p) in owner]
+
     def _ema_params(self):
         """[(state_dict key, optimiser, index)] of every parameter that has an EMA"""
-        owner = {id(p): (opt, i) for opt in self.optimizers.values() if opt.ema is not None for i, p in enumerate(opt.params)}
-        return [(name,) + owner[id(p)] for name, p in self.model.named_parameters() if id(p) in owner]
+        return self._owned_params(ema_only=True)
 
     def ema_model_state(self):
         """``model_state_dict`` with the averaged parameters replaced by their EMA (same keys; None: no optimiser keeps an EMA)"""
@@ -410,6 +417,47 @@ class Trainer(object):
             for k, x in zip(losses.keys(), vals):
                 tb.add_scalar('train/%s' % k, x, global_step)
             tb.flush()
+
+    # -- per-tensor histograms (SYS.HISTOGRAM_INTERVAL) ----------------------------------------------------------
+    def write_histograms(self, global_step):
+        """SYS.HISTOGRAM_INTERVAL N, master process, train steps with global_step % N == 0: weights/<name>, grads/<name> (and ema/<name>)
+        histograms, weight_norm/<name> and grad_norm/<name> scalars (the square root of the histogram's own sum of squares) and
+        nonfinite/<name> (the number of NaN and inf entries of the weights and the gradient, only when there are any) for every
+        parameter an optimiser owns.  Called after ``graphed_or_eager_step`` has returned: eager launches on the current stream, outside
+        any captured graph and after ops.join_side_stream(); no collective.  flat_grad still holds this step's exchanged gradient here:
+        zero_grad runs at the start of the NEXT step.  One device-to-host copy per optimiser buffer."""
+        n = getattr(self.cfg.SYS, 'HISTOGRAM_INTERVAL', None)
+        tb = getattr(self, 'tb_writer', None)
+        if n is None or tb is None or global_step % n != 0 or not self.is_master_process():
+            return
+        from ... import ops, tensor_hist
+        ops.join_side_stream()
+        names = {}
+        for name, opt, i in self._owned_params():
+            names.setdefault(id(opt), (opt, {}))[1][i] = name
+        packed = []
+        for opt, _ in names.values():  # every launch first, then the copies
+            for prefix, which in (('weights', 'param'), ('grads', 'grad'), ('ema', 'ema')):
+                if which == 'ema' and opt.ema is None:
+                    continue
+                counts, tallies, stats = tensor_hist.optimizer_histograms(opt, which)
+                packed.append((opt, prefix, torch.cat([counts, tallies, stats.view(torch.int64)], dim=1)))
+        nonfinite = {}
+        for opt, prefix, dev_rows in packed:
+            rows = dev_rows.cpu().numpy()  # (the one copy of this buffer's results)
+            nb = tensor_hist.NUM_BUCKETS
+            for i, name in sorted(names[id(opt)][1].items()):
+                counts, tallies, stats = rows[i, :nb], rows[i, nb:nb + 3], rows[i, nb + 3:].view(np.float64)
+                fields = tensor_hist.to_proto_fields(counts, tallies, stats)
+                if fields is not None:  # (a tensor without a finite element has no histogram: its tallies say why)
+                    tb.add_histogram_raw('%s/%s' % (prefix, name), *fields, step=global_step)
+                if prefix != 'ema':
+                    tb.add_scalar('%s_norm/%s' % (prefix[:-1], name), float(np.sqrt(stats[3])), global_step)
+                    nonfinite[name] = nonfinite.get(name, 0) + int(tallies[1] + tallies[2])
+        for name, bad in nonfinite.items():
+            if bad:
+                tb.add_scalar('nonfinite/%s' % name, bad, global_step)
+        tb.flush()
 
     def tb_epoch_scalars(self, prefix, values, epoch):
         """SYS.TENSORBOARD: ``<prefix>/<k>`` at step = epoch (trainer.py:279-280, 291-294)"""

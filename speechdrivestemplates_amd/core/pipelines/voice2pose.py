@@ -318,6 +318,7 @@ class Voice2Pose(Trainer):
         # static inputs and launches ONE graph instead of ~270 kernels -- on one GPU and under data parallelism alike (graph.GraphedStep captures the
         # RCCL all-reduces with the step, or replays two graphs around an eager exchange; steps that save results run eagerly: they need the final poses)
         losses, results = self.graphed_or_eager_step(batch, eager_ok=not save_step, want_final=bool(save_step))
+        self.write_histograms(global_step)  # (SYS.HISTOGRAM_INTERVAL: after the step, outside the captured graph)
         self.last_losses = losses
         if log_step:
             if self.cfg.SYS.DISTRIBUTED:

@@ -2068,3 +2068,49 @@ def adam_step_guarded(p, g, m, v, lr_dev, state_dev, guard, beta1=0.9, beta2=0.9
             raise ValueError('the EMA buffer must match the parameter buffer')
     check(_lib.load().sdt_adam_step_guarded_f32(_p(p), _p(g), _p(m), _p(v), p.numel(), _p(lr_dev), beta1, beta2, eps, weight_decay,
                                                 _p(guard), _p(ema), ema_decay, _p(state_dev), _stream()))
+
+
+# --------------------------------------------------------------------------------------------
+# Per-tensor histograms and moments of a flat buffer (csrc/tensor_hist.hip; tensor_hist.py is the interface)
+def _check_sizes(status):
+    """as ``check``; the library's "unsupported size" status becomes a ValueError"""
+    if status == -3:  # SDT_ERR_UNSUPPORTED
+        raise ValueError('libsdt_hip: %s' % _lib.load().sdt_last_error().decode())
+    check(status)
+
+
+def tensor_hist_constants():
+    """launch constants of the library as built: {'threads', 'chunk', 'buckets', 'max_segments'}"""
+    lib = _lib.load()
+    return {k: int(getattr(lib, 'sdt_tensor_hist_' + k)()) for k in ('threads', 'chunk', 'buckets', 'max_segments')}
+
+
+def tensor_hist_plan(offsets, sizes, n):
+    """Host side (no GPU): the segment table (S, 3) {offset, numel, first chunk} and the chunk table (C, 2) {segment, chunk number} of a
+    flat buffer of ``n`` elements, int64 CPU tensors.  ValueError for sizes the kernel does not take."""
+    import ctypes as C
+    lib = _lib.load()
+    S = len(offsets)
+    if len(sizes) != S:
+        raise ValueError('tensor_hist_plan: %d offsets but %d sizes' % (S, len(sizes)))
+    segs = torch.tensor([[int(o), int(s)] for o, s in zip(offsets, sizes)], dtype=torch.int64).reshape(S, 2)
+    n_chunks = C.c_int64(0)
+    _check_sizes(lib.sdt_tensor_hist_plan(_p(segs) if S else None, S, int(n), None, None, 0, C.addressof(n_chunks)))
+    seg_plan = torch.zeros((S, 3), dtype=torch.int64)
+    chunk_plan = torch.zeros((max(1, n_chunks.value), 2), dtype=torch.int64)
+    _check_sizes(lib.sdt_tensor_hist_plan(_p(segs), S, int(n), _p(seg_plan), _p(chunk_plan), n_chunks.value, C.addressof(n_chunks)))
+    return seg_plan, chunk_plan[:n_chunks.value]
+
+
+def tensor_hist(flat, seg_plan, chunk_plan, edges, scale, counts, tallies, stats, partials):
+    """one segmented pass over the fp32 buffer ``flat`` on the current stream (tables, edges and outputs are device tensors)"""
+    _req_cuda(flat, seg_plan, chunk_plan, edges, counts, tallies, stats, partials)
+    S, nc = seg_plan.shape[0], chunk_plan.shape[0]
+    if flat.dtype != torch.float32 or not flat.is_contiguous():
+        raise ValueError('tensor_hist: flat must be a contiguous fp32 buffer')
+    if counts.dtype != torch.int64 or tallies.dtype != torch.int64 or stats.dtype != torch.float64 or edges.dtype != torch.float64 \
+            or counts.numel() < S * (edges.numel() - 1) or tallies.numel() < 3 * S or stats.numel() < 4 * S or partials.numel() < 4 * nc \
+            or partials.dtype != torch.float64:
+        raise ValueError('tensor_hist: output buffers of the wrong type or size')
+    _check_sizes(_lib.load().sdt_tensor_hist_f32(_p(flat), flat.numel(), _p(seg_plan), S, _p(chunk_plan), nc, _p(edges), edges.numel(),
+                                                 float(scale), _p(counts), _p(tallies), _p(stats), _p(partials), _stream()))

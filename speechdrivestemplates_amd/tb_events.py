@@ -7,12 +7,14 @@ File: ``<log_dir>/events.out.tfevents.<10-digit unix time>.<hostname>``, a seque
 whose data are hand-encoded protobuf messages:
     Event          1 wall_time double, 2 step int64, 3 file_version string, 5 summary
     Summary        repeated 1 value
-    Summary.Value  1 tag string, 2 simple_value float, 4 image
+    Summary.Value  1 tag string, 2 simple_value float, 4 image, 5 histo
     Summary.Image  1 height, 2 width, 3 colorspace, 4 encoded_image_string
+    HistogramProto 1 min, 2 max, 3 num, 4 sum, 5 sum_squares (doubles), 6 bucket_limit, 7 bucket (packed repeated doubles)
 The first record is Event{wall_time, file_version: "brain.Event:2"}.  A GIF inside an image summary is what ``add_video`` produces.
 
     python -m speechdrivestemplates_amd.tb_events FILE [--extract DIR]
-        one line per record: step, tag, then the value or ``image HxW <n> bytes``; --extract writes the embedded PNG / GIF files to DIR
+        one line per record: step, tag, then the value, ``image HxW <n> bytes`` or ``histogram num=... min=... max=... mean=... std=...
+        buckets=...``; --extract writes the embedded PNG / GIF files, and every histogram as an .npz, to DIR
 """
 import os
 import socket
@@ -90,6 +92,16 @@ def image_summary(tag, encoded, height, width, colorspace=3):
     return _f_bytes(1, _f_bytes(1, tag) + _f_bytes(4, image))
 
 
+def histogram_summary(tag, min, max, num, sum, sum_squares, bucket_limit, bucket):
+    """``bucket_limit``: the right edge of every bucket, ``bucket``: its count (tensor_hist.to_proto_fields makes both)"""
+    bucket_limit, bucket = [float(x) for x in bucket_limit], [float(x) for x in bucket]
+    if len(bucket_limit) != len(bucket):
+        raise ValueError("a histogram has one limit per bucket, got %d limits and %d buckets" % (len(bucket_limit), len(bucket)))
+    histo = b"".join(_key(i + 1, 1) + struct.pack("<d", float(v)) for i, v in enumerate((min, max, num, sum, sum_squares)))
+    histo += _f_bytes(6, struct.pack("<%dd" % len(bucket_limit), *bucket_limit)) + _f_bytes(7, struct.pack("<%dd" % len(bucket), *bucket))
+    return _f_bytes(1, _f_bytes(1, tag) + _f_bytes(5, histo))
+
+
 def record(data):
     head = struct.pack("<Q", len(data))
     return head + struct.pack("<I", masked_crc32c(head)) + data + struct.pack("<I", masked_crc32c(data))
@@ -121,6 +133,11 @@ class EventWriter(object):
     def add_image_bytes(self, tag, encoded, height, width, step, colorspace=3):
         """an already encoded PNG or GIF file as an image summary"""
         self._write(_event(time.time(), step=int(step), summary=image_summary(tag, encoded, height, width, colorspace)))
+
+    def add_histogram_raw(self, tag, min, max, num, sum, sum_squares, bucket_limit, bucket, step):
+        """an already binned histogram (SummaryWriter.add_histogram_raw)"""
+        self._write(_event(time.time(), step=int(step),
+                           summary=histogram_summary(tag, min, max, num, sum, sum_squares, bucket_limit, bucket)))
 
     def flush(self):
         with self._lock:
@@ -197,8 +214,26 @@ def read_records(path):
     return out
 
 
+def _doubles(wire, x):
+    """a repeated double field: packed (wire type 2) or one element (wire type 1)"""
+    if wire == 2 and len(x) % 8:
+        raise CorruptFile("packed doubles of %d bytes" % len(x))
+    return list(struct.unpack("<%dd" % (len(x) // 8), x)) if wire in (1, 2) else []
+
+
+def _read_histo(buf):
+    histo = {"min": 0.0, "max": 0.0, "num": 0.0, "sum": 0.0, "sum_squares": 0.0, "bucket_limit": [], "bucket": []}
+    for f, w, x in _fields(buf):
+        if w == 1 and 1 <= f <= 5:
+            histo[("min", "max", "num", "sum", "sum_squares")[f - 1]], = struct.unpack("<d", x)
+        elif f in (6, 7):
+            histo["bucket_limit" if f == 6 else "bucket"] += _doubles(w, x)
+    return histo
+
+
 def read_events(path):
-    """-> [{'wall_time', 'step', 'file_version' or None, 'values': [{'tag', 'simple_value'} | {'tag', 'image': {...}}]}]"""
+    """-> [{'wall_time', 'step', 'file_version' or None, 'values': [{'tag', 'simple_value'} | {'tag', 'image': {...}} |
+    {'tag', 'histo': {'min', 'max', 'num', 'sum', 'sum_squares', 'bucket_limit', 'bucket'}}]}]"""
     events = []
     for data in read_records(path):
         ev = {"wall_time": None, "step": 0, "file_version": None, "values": []}
@@ -227,6 +262,8 @@ def read_events(path):
                                 elif f4 == 4 and w4 == 2:
                                     img["encoded"] = bytes(y)
                             item["image"] = img
+                        elif f3 == 5 and w3 == 2:
+                            item["histo"] = _read_histo(x)
                     ev["values"].append(item)
         events.append(ev)
     return events
@@ -242,6 +279,12 @@ def describe(events):
             if "image" in item:
                 img = item["image"]
                 lines.append("%d %s image %dx%d %d bytes" % (ev["step"], item["tag"], img["height"], img["width"], len(img["encoded"])))
+            elif "histo" in item:
+                h = item["histo"]
+                mean = h["sum"] / h["num"] if h["num"] else float("nan")
+                std = max(h["sum_squares"] / h["num"] - mean * mean, 0.0) ** 0.5 if h["num"] else float("nan")
+                lines.append("%d %s histogram num=%d min=%.9g max=%.9g mean=%.9g std=%.9g buckets=%d"
+                             % (ev["step"], item["tag"], h["num"], h["min"], h["max"], mean, std, len(h["bucket"])))
             else:
                 lines.append("%d %s %.9g" % (ev["step"], item["tag"], item.get("simple_value", float("nan"))))
     return lines
@@ -255,7 +298,7 @@ def main(argv=None):
     import argparse
     ap = argparse.ArgumentParser(description="list the records of a TensorBoard event file")
     ap.add_argument("file")
-    ap.add_argument("--extract", metavar="DIR", help="write the embedded PNG and GIF files to DIR")
+    ap.add_argument("--extract", metavar="DIR", help="write the embedded PNG and GIF files, and every histogram as an .npz, to DIR")
     a = ap.parse_args(argv)
     events = read_events(a.file)
     print("\n".join(describe(events)))
@@ -269,6 +312,11 @@ def main(argv=None):
                     name = "%04d_step%d_%s%s" % (n, ev["step"], item["tag"].replace("/", "_"), _extension(enc))
                     with open(os.path.join(a.extract, name), "wb") as f:
                         f.write(enc)
+                    n += 1
+                elif "histo" in item:
+                    import numpy as np
+                    name = "%04d_step%d_%s.npz" % (n, ev["step"], item["tag"].replace("/", "_"))
+                    np.savez(os.path.join(a.extract, name), **{k: np.asarray(v, dtype=np.float64) for k, v in item["histo"].items()})
                     n += 1
         print("extracted %d files to %s" % (n, a.extract))
 
