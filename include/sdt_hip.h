@@ -361,6 +361,30 @@ int sdt_chain1d_bwd_f32(const sdt_chain1d_layer* layers, int nlayers, const floa
 /* nn.L1Loss(reduction='none')(pred,gt)*lambda .mean() (voice2pose.py:141-142). partial: >=256 doubles. */
 int sdt_l1_loss_fwd_f32(const float* pred, const float* gt, int64_t n, float lambda, double* partial, float* loss, void* stream);
 int sdt_l1_loss_bwd_f32(const float* pred, const float* gt, const float* gout, int64_t n, float lambda, float* dpred, void* stream);
+/*
+ * The L1 loss with a confidence mask, per-channel weights and a velocity term (csrc/reg_loss.hip), on (B, T, C) fp32:
+ *   e = double(pred) - double(gt);  d[b,t,c] = e[b,t+1,c] - e[b,t,c] for t < T-1
+ *   m = score > min_conf ? 1 : 0 (score NULL: 1 everywhere, min_conf unused; the comparison is strict);  m2[b,t,c] = m[b,t,c] * m[b,t+1,c]
+ *   w[c] = chan_w[c] (C floats; NULL: 1)
+ *   losses[0] = lambda_reg * sum(m * w * |e|) / max(sum m, 1);   losses[1] = lambda_vel * sum(m2 * w * |d|) / max(sum m2, 1)
+ * The denominators count live elements (the weights are not in them); an empty sum gives exactly 0.  Sums are float64 per-block partials
+ * combined by one block in a fixed order, counts are exact integers, no atomics: two calls give the same bits.  Masked elements are selected
+ * away, so whatever sits under the mask (NaN included) reaches neither a loss nor a gradient.  Nothing is read on the host: forward leaves
+ * denom[0..1] = the two denominators on the device and backward divides by them.
+ *   partial: >= 512 doubles, counts: >= 512 int64 (workspaces, contents irrelevant);  losses: 2 floats;  denom: 2 doubles.
+ * Forward is two launches (partials, final block), backward one:
+ *   kr = (gout_reg / denom[0]) * lambda_reg * w;   kv = (gout_vel / denom[1]) * lambda_vel * w      (float64, in this order)
+ *   dpred = (float)(kr * m * sign(e) + kv * m2[t-1] * sign(d[t-1]) - kv * m2[t] * sign(d[t]))
+ * with sign(0) = 0, terms of frames outside [0, T) absent, everything in float64 and rounded once.  The order is the one torch's autograd
+ * takes on the float64 expression above, so terms that cancel there cancel here to the same exact 0.  gout_reg / gout_vel: one device
+ * float each, NULL = that loss has no upstream gradient (its term is 0).
+ */
+int sdt_reg_loss_fwd_f32(const float* pred, const float* gt, const float* score, const float* chan_w, int B, int T, int C,
+                         double lambda_reg, double lambda_vel, float min_conf, double* partial, int64_t* counts, float* losses,
+                         double* denom, void* stream);
+int sdt_reg_loss_bwd_f32(const float* pred, const float* gt, const float* score, const float* chan_w, const float* gout_reg,
+                         const float* gout_vel, const double* denom, int B, int T, int C, double lambda_reg, double lambda_vel,
+                         float min_conf, float* dpred, void* stream);
 /* LSGAN terms (voice2pose.py:171-189, nn.MSELoss against a constant): loss = lambda * mean((scores - target)^2);
  * dscores = gout * 2 * lambda / n * (scores - target). */
 int sdt_mse_const_fwd_f32(const float* scores, int64_t n, float target, float lambda, float* loss, void* stream);

@@ -13,6 +13,14 @@ _DEFAULTS = {
         "STRICT_LOADING": True,
         "GENERATOR": {
             "NAME": None, "LEAKY_RELU": True, "NORM": "IN", "LAMBDA_REG": 1.0, "LAMBDA_CLIP_KL": 0.1,
+            # extensions (the regression loss on noisy keypoints, ops.RegLossFn / csrc/reg_loss.hip; the defaults are the
+            # reference's plain mean, computed by the same kernels as before):
+            # LAMBDA_VEL >= 0: weight of G_vel_loss, an L1 on the first differences over time of (prediction - ground truth).
+            # REG_MIN_CONFIDENCE: a float c = an element takes part in G_reg_loss (and a pair of frames in G_vel_loss) only where the batch's
+            # 'poses_score' (the OpenPose confidence) is > c; each sum is divided by the number of elements that took part.  None masks nothing.
+            # REG_PART_WEIGHTS: [body, face, hands], three floats >= 0 that multiply the terms of keypoints 0-8 / 9-78 / 79-120 (not the
+            # divisors).  None = 1 everywhere.
+            "LAMBDA_VEL": 0.0, "REG_MIN_CONFIDENCE": None, "REG_PART_WEIGHTS": None,
             "CLIP_CODE": {"DIMENSION": None, "LR_SCALING": 1.0, "TRAIN": True, "FRAME_VARIANT": False,
                           "SAMPLE_FROM_NORMAL": False, "TEST_WITH_GT_CODE": False, "EXTERNAL_CODE": False,
                           "EXTERNAL_CODE_PTH": None},
@@ -173,6 +181,30 @@ def check_optim_guard(cfg, checkpoint_has_ema=False):
     if cfg.SYS.EVAL_WITH_EMA and decay is None and not checkpoint_has_ema:
         raise ValueError("SYS.EVAL_WITH_EMA needs an EMA to evaluate: set TRAIN.EMA_DECAY, or load a checkpoint that carries "
                          "'model_ema_state_dict' (one written by a run with TRAIN.EMA_DECAY)")
+
+
+def _is_number(v):
+    return isinstance(v, (int, float)) and not isinstance(v, bool) and v == v and abs(v) != float('inf')
+
+
+def check_reg_loss(cfg):
+    """Validate VOICE2POSE.GENERATOR.LAMBDA_VEL / REG_MIN_CONFIDENCE / REG_PART_WEIGHTS.  Returns None when all three are at their defaults
+    (the plain L1 mean), else (lambda_vel, min_confidence or None, (body, face, hands) or None) as Python floats."""
+    g = cfg.VOICE2POSE.GENERATOR
+    vel, conf, parts = g.LAMBDA_VEL, g.REG_MIN_CONFIDENCE, g.REG_PART_WEIGHTS
+    pre = "VOICE2POSE.GENERATOR."
+    if not _is_number(vel) or vel < 0:
+        raise ValueError(pre + "LAMBDA_VEL must be a number >= 0, got %r" % (vel,))
+    if conf is not None and not _is_number(conf):
+        raise ValueError(pre + "REG_MIN_CONFIDENCE must be None or a number, got %r" % (conf,))
+    if parts is not None:
+        if not isinstance(parts, (list, tuple)) or len(parts) != 3:
+            raise ValueError(pre + "REG_PART_WEIGHTS must be None or three numbers [body, face, hands], got %r" % (parts,))
+        if not all(_is_number(w) and w >= 0 for w in parts):
+            raise ValueError(pre + "REG_PART_WEIGHTS: every weight must be a number >= 0, got %r" % (parts,))
+    if vel == 0 and conf is None and parts is None:
+        return None
+    return float(vel), None if conf is None else float(conf), None if parts is None else tuple(float(w) for w in parts)
 
 
 def check_histograms(cfg):

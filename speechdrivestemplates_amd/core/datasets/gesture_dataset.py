@@ -112,6 +112,14 @@ class PoseTransforms:
             PoseTransforms._PART_INDEX[key] = (torch.tensor(sel, dtype=torch.int64, device=device), torch.tensor(root, dtype=torch.int64, device=device))
         return PoseTransforms._PART_INDEX[key]
 
+    BODY, FACE, HANDS = 0, 1, 2
+
+    @staticmethod
+    def part_table():
+        """The part of each of the 121 keypoints (pose_definition.md): BODY 0-8 (upper body and eyes), FACE 9-78 (HEAD_ROOT, the root the
+        other 69 hang off in ``_part_index``, is a face keypoint), HANDS 79-120 (left 79-99, right 100-120)."""
+        return [PoseTransforms.BODY] * 9 + [PoseTransforms.FACE] * 70 + [PoseTransforms.HANDS] * 42
+
     def parted_to_global(self, poses):
         """gesture_dataset.py:147-155, in place: head / hand keypoints += their part's root (the roots themselves are in no part)."""
         sel, root = self._part_index(poses.device)

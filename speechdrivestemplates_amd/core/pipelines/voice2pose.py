@@ -17,8 +17,10 @@ import torch
 from torch import nn
 
 from ... import dp, ops
+from ...config import check_reg_loss
 from ...mel import MelSpectrogram
 from ...optim import FlatAdam
+from ..datasets.gesture_dataset import PoseTransforms
 from ..networks import get_model
 from .trainer import Trainer
 
@@ -27,6 +29,9 @@ class Voice2PoseModel(nn.Module):
     def __init__(self, cfg, state_dict=None, num_train_samples=None, rank=0, external_codes=None) -> None:
         super().__init__()
         self.cfg = cfg
+        # LAMBDA_VEL / REG_MIN_CONFIDENCE / REG_PART_WEIGHTS, validated; None = all at their defaults: the plain L1 mean (ops.L1LossFn)
+        self.reg_opts = check_reg_loss(cfg)
+        self._chan_w = {}  # device -> per-channel part weights (2 * 121 floats, x then y), built once
         self.mel_transfm = MelSpectrogram(win_length=400, hop_length=160, n_fft=512, f_min=55, f_max=7500.0, n_mels=80)
         self.netG = get_model(cfg.VOICE2POSE.GENERATOR.NAME)(cfg)
         code = cfg.VOICE2POSE.GENERATOR.CLIP_CODE
@@ -74,6 +79,19 @@ class Voice2PoseModel(nn.Module):
         if self.clips_code.device != dev:  # plain-tensor external codes are not moved by .cuda()
             self.clips_code = self.clips_code.to(dev)
         return self.clips_code
+
+    def _chan_weights(self, dev):
+        """REG_PART_WEIGHTS spread over the (2, 121) channels of a pose frame, on ``dev`` (None: unit weights); uploaded once per device,
+        like PoseTransforms._part_index -- no host-to-device copy inside a step, which a hipGraph capture would refuse"""
+        parts = self.reg_opts[2]
+        if parts is None:
+            return None
+        key = str(dev)
+        if key not in self._chan_w:
+            per_kp = [parts[p] for p in PoseTransforms.part_table()]
+            assert len(per_kp) == self.cfg.DATASET.NUM_LANDMARKS
+            self._chan_w[key] = torch.tensor(per_kp * 2, dtype=torch.float32, device=dev)
+        return self._chan_w[key]
 
     def _eval_code(self, batch, n, dev, poses_gt, dataset, speaker, interpolation_coeff, return_loss):
         """Code selection outside training (voice2pose.py:95-120)."""
@@ -128,9 +146,19 @@ class Voice2PoseModel(nn.Module):
         results['poses_gt_batch'] = poses_gt
 
         losses = {}
-        reg = ops.L1LossFn.apply(poses_pred, poses_gt, float(g.LAMBDA_REG))  # voice2pose.py:141-142
-        losses['G_reg_loss'] = reg
-        g_loss = reg
+        if self.reg_opts is None:
+            reg = ops.L1LossFn.apply(poses_pred, poses_gt, float(g.LAMBDA_REG))  # voice2pose.py:141-142
+            losses['G_reg_loss'] = reg
+            g_loss = reg
+        else:  # masked / part-weighted L1 and the velocity term in one fused op
+            lam_vel, min_conf, _ = self.reg_opts
+            score = batch['poses_score'].to(dev, non_blocking=True) if min_conf is not None else None
+            reg, vel = ops.RegLossFn.apply(poses_pred, poses_gt, score, self._chan_weights(dev), float(g.LAMBDA_REG), lam_vel, min_conf)
+            losses['G_reg_loss'] = reg
+            g_loss = reg
+            if lam_vel > 0:
+                losses['G_vel_loss'] = vel
+                g_loss = g_loss + vel
         if kl is not None:
             losses['G_clipcode_kl_loss'] = kl
             results['kl_valid'] = kl_valid

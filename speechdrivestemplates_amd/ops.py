@@ -1814,6 +1814,52 @@ class L1LossFn(torch.autograd.Function):
         return dp, None, None
 
 
+class RegLossFn(torch.autograd.Function):
+    """L1LossFn with a confidence mask, per-channel weights and a velocity term (csrc/reg_loss.hip):
+    (reg, vel) = (lam_reg * sum(m w |e|) / max(sum m, 1), lam_vel * sum(m2 w |d|) / max(sum m2, 1)) with e = pred - gt on (B, T, ...),
+    d its first difference over T, m = score > min_conf (score None: 1), m2 the product of a pair's two m, w = chan_w per trailing
+    element (None: 1).  Two launches forward, one backward; the divisors stay on the device."""
+
+    @staticmethod
+    def forward(ctx, pred, gt, score, chan_w, lam_reg, lam_vel, min_conf):
+        _req_cuda(pred, gt)
+        assert pred.dim() >= 3 and pred.shape == gt.shape and pred.dtype == gt.dtype == torch.float32
+        pred, gt = pred.contiguous(), gt.contiguous()
+        B, T = pred.shape[0], pred.shape[1]
+        C = pred.numel() // (B * T)
+        if score is not None:
+            _req_cuda(score)
+            assert score.shape == pred.shape and score.dtype == torch.float32 and min_conf is not None
+            score = score.contiguous()
+        if chan_w is not None:
+            _req_cuda(chan_w)
+            assert chan_w.shape == (C,) and chan_w.dtype == torch.float32 and chan_w.is_contiguous()
+        dev = pred.device
+        partial = torch.empty(512, device=dev, dtype=torch.float64)
+        counts = torch.empty(512, device=dev, dtype=torch.int64)
+        losses = torch.empty(2, device=dev, dtype=torch.float32)
+        denom = torch.empty(2, device=dev, dtype=torch.float64)
+        ctx.args = (B, T, C, float(lam_reg), float(lam_vel), 0.0 if score is None else float(min_conf))
+        check(_lib.load().sdt_reg_loss_fwd_f32(_p(pred), _p(gt), _p(score), _p(chan_w), *ctx.args, _p(partial), _p(counts), _p(losses),
+                                               _p(denom), _stream()))
+        ctx.save_for_backward(pred, gt, score, chan_w, denom)
+        ctx.set_materialize_grads(False)  # backward takes None for a loss that nothing consumed
+        reg, vel = losses.unbind(0)
+        return reg, vel
+
+    @staticmethod
+    def backward(ctx, g_reg, g_vel):
+        pred, gt, score, chan_w, denom = ctx.saved_tensors
+        if g_reg is None and g_vel is None:
+            return (None,) * 7
+        dp = torch.empty_like(pred)
+        g_reg = None if g_reg is None else g_reg.contiguous()
+        g_vel = None if g_vel is None else g_vel.contiguous()
+        check(_lib.load().sdt_reg_loss_bwd_f32(_p(pred), _p(gt), _p(score), _p(chan_w), _p(g_reg), _p(g_vel), _p(denom), *ctx.args,
+                                               _p(dp), _stream()))
+        return (dp,) + (None,) * 6
+
+
 class MseConstFn(torch.autograd.Function):
     """lambda * mean((scores - target)^2): the LSGAN generator / discriminator terms (voice2pose.py:171-189)."""
 
