@@ -802,6 +802,40 @@ int sdt_tensor_hist_f32(const float* flat, int64_t n, const int64_t* seg_plan, i
                         const double* edges, int n_edges, float scale, int64_t* counts, int64_t* tallies, double* stats, double* partials,
                         void* stream);
 
+/*
+ * Per-clip validation metrics on final float64 poses (TEST.CLIP_METRICS; speechdrivestemplates_amd/clip_metrics.py; DESIGN.md section 22 is
+ * the contract, clip_metrics.clip_metrics_model / epoch_model are the same operations in numpy).  pred / gt: (R, T, 2, K) float64, parts: K
+ * bytes in {0, 1, 2} (body, face, hands); part index p = 0 is "all", p = 1 + byte.  Every multiply, add and subtract is rounded on its own
+ * (csrc/exact_f64.h); no floating-point atomics.  No allocation; every pointer except ``alphas``, ``part_sizes`` and ``tables`` (host arrays,
+ * read during the call) is a device buffer; every size is checked before the launch.
+ *   A record is 40 words of 8 bytes: float64 [0,4) l2_sum[p], [4,8) speed_pred[p], [8,12) speed_gt[p], [12,16) vel_l2[p], [16,20) div_sum[p];
+ *   int64 [20,36) pck_hit[a * 4 + p] (a >= A: 0), 36 seen, 37 copies, 38 nonfinite, 39 frames.
+ *   rows: one record per row (div_sum 0, seen 1, copies 1) into rows (R x 40 words); work: R * T * 32 words, contents irrelevant.  Within a
+ *     frame lane k holds keypoint k's term (0 outside the part) and the 128 lanes are combined by the xor butterfly 32, 16, 8, 4, 2, 1 inside
+ *     each wave, then wave 0 + wave 1; the frames of a row are added in frame order.  K in [1, 128], T >= 1, A in [1, 4].
+ *   diversity: row j * B + b is copy j of clip b, m in [2, 16]; lane k adds its pair terms in lexicographic (i, j) order, the butterfly
+ *     combines the lanes; divwork: B * T * 4 float64 (per (clip, frame), summed over t in order by commit).
+ *   commit: the m row records of clip b added in order j = 0..m-1, div_sum from divwork (NULL with m = 1), into row clip_index[b] of table,
+ *     (N + 1) x 40 words: row N is the header, whose word 0 counts the indices outside [0, N) (they write nothing else).  Two entries of one
+ *     call with the same index: either may win.
+ *   epoch: tables are ranks (1..64) table pointers; clip n takes the record of the lowest rank with seen set, records with nonfinite set are
+ *     left out and counted.  Columns are summed in chunks of 64 clips in index order, then the chunk partials in order.  work:
+ *     ceil(N / 64) * 48 words.  out (40 words): float64 [0,4) L2[p], [4,20) PCK[a * 4 + p], [20,24) mean over the alphas of PCK[.][p],
+ *     [24,28) sum speed_pred[p] / sum speed_gt[p], [28,32) vel_L2[p], [32,36) diversity[p]; int64 36 clips with a record, 37 of them left
+ *     out as nonfinite, 38 index errors of all tables, 39 the number of (pair, frame) terms behind diversity.  A quotient whose divisor is 0
+ *     is 0.0.  part_sizes: 4 int64 {K, body, face, hands}.
+ *   sqrt: y[i] = sqrt(x[i]) as the kernels above compute it (the tests ask it whether this device's square root is correctly rounded).
+ */
+#define SDT_CLIP_METRICS_COLS 40
+int sdt_clip_metrics_rows_f64(const double* pred, const double* gt, const uint8_t* parts, const double* alphas, int num_alphas, int R, int T,
+                              int K, void* work, void* rows, void* stream);
+int sdt_clip_metrics_diversity_f64(const double* pred, const uint8_t* parts, int B, int m, int T, int K, double* divwork, void* stream);
+int sdt_clip_metrics_commit(const void* rows, const double* divwork, const int64_t* clip_index, int B, int m, int T, void* table, int64_t N,
+                            void* stream);
+int sdt_clip_metrics_epoch(const void* const* tables, int ranks, int64_t N, const int64_t* part_sizes, int num_alphas, void* work, void* out,
+                           void* stream);
+int sdt_clip_metrics_sqrt_f64(const double* x, int64_t n, double* y, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -179,6 +179,11 @@ SIGNATURES = {
     "sdt_tensor_hist_max_segments": [],
     "sdt_tensor_hist_plan": [_p, _i, _i64, _p, _p, _i64, _p],
     "sdt_tensor_hist_f32": [_p, _i64, _p, _i, _p, _i64, _p, _i, _f, _p, _p, _p, _p, _p],
+    "sdt_clip_metrics_rows_f64": [_p, _p, _p, C.POINTER(C.c_double), _i, _i, _i, _i, _p, _p, _p],
+    "sdt_clip_metrics_diversity_f64": [_p, _p, _i, _i, _i, _i, _p, _p],
+    "sdt_clip_metrics_commit": [_p, _p, _p, _i, _i, _i, _p, _i64, _p],
+    "sdt_clip_metrics_epoch": [C.POINTER(C.c_void_p), _i, _i64, C.POINTER(C.c_int64), _i, _p, _p, _p],
+    "sdt_clip_metrics_sqrt_f64": [_p, _i64, _p, _p],
 }
 F32, BF16 = 0, 1  # enum sdt_dtype
 

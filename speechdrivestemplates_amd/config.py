@@ -56,7 +56,15 @@ _DEFAULTS = {
               # pose2pose's optimiser), updated after every applied step and saved as 'model_ema_state_dict'.  The discriminator and the
               # BatchNorm running statistics (buffers) are not averaged.
               "GRAD_CLIP_NORM": None, "SKIP_NONFINITE_STEP": False, "EMA_DECAY": None},
-    "TEST": {"BATCH_SIZE": 32, "NUM_RESULT_SAMPLE": 8, "SAVE_VIDEO": True, "SAVE_NPZ": True, "MULTIPLE": 1},
+    "TEST": {"BATCH_SIZE": 32, "NUM_RESULT_SAMPLE": 8, "SAVE_VIDEO": True, "SAVE_NPZ": True, "MULTIPLE": 1,
+             # extensions (per-clip validation metrics, clip_metrics.ClipMetricsAccumulator / csrc/clip_metrics.hip; DESIGN.md section 22;
+             # Voice2Pose only).  CLIP_METRICS True = every test_step also commits its clips' records (keypoint-distance, PCK-hit, speed,
+             # velocity-error and, with MULTIPLE > 1, pairwise-diversity sums per body part) to a table on the GPU, and validate() / test() add
+             # PCK_<alpha>, PCK, PCK_hands, L2_body / L2_face / L2_hands, speed_ratio, speed_ratio_hands, vel_L2, diversity, diversity_hands
+             # and clips_nonfinite to their values: over the tables of ALL ranks (one all-gather), the same bits on every rank.  With SAVE_NPZ
+             # the master also writes results/epoch<E>-<TAG>-clip_metrics.npz (the table, its column names, the alphas).  False = the loop
+             # as it was.  PCK_ALPHAS: one to four thresholds > 0, as fractions of the larger side of the ground truth's bounding box.
+             "CLIP_METRICS": False, "PCK_ALPHAS": [0.1, 0.2]},
     "DEMO": {"MULTIPLE": 1, "NUM_SAMPLES": 1, "CODE_INDEX": None, "CODE_INDEX_B": None, "CODE_PATH": None},
     "SYS": {"OUTPUT_DIR": "output/", "CANVAS_SIZE": (720, 1280), "VISUALIZATION_SCALING": 0.85,
             "VIDEO_FORMAT": ["mp4", "img"], "ASYNC_VIDEO_SAVING": False, "LOG_INTERVAL": 100, "NUM_WORKERS": 8,
@@ -205,6 +213,26 @@ def check_reg_loss(cfg):
     if vel == 0 and conf is None and parts is None:
         return None
     return float(vel), None if conf is None else float(conf), None if parts is None else tuple(float(w) for w in parts)
+
+
+def check_clip_metrics(cfg):
+    """Validate TEST.CLIP_METRICS / TEST.PCK_ALPHAS.  Returns None with the key off, else the alphas as a tuple of Python floats."""
+    on, alphas = cfg.TEST.CLIP_METRICS, cfg.TEST.PCK_ALPHAS
+    if not isinstance(on, bool):
+        raise ValueError("TEST.CLIP_METRICS must be True or False, got %r" % (on,))
+    if not isinstance(alphas, (list, tuple)) or not 1 <= len(alphas) <= 4:
+        raise ValueError("TEST.PCK_ALPHAS must be a list of one to four numbers, got %r" % (alphas,))
+    if not all(_is_number(a) and a > 0 for a in alphas):
+        raise ValueError("TEST.PCK_ALPHAS: every alpha must be a finite number > 0, got %r" % (alphas,))
+    if not on:
+        return None
+    if cfg.PIPELINE_TYPE != "Voice2Pose":
+        raise ValueError("TEST.CLIP_METRICS is a Voice2Pose key (PCK, part errors, speed and diversity of predicted gestures), got "
+                         "PIPELINE_TYPE %r" % (cfg.PIPELINE_TYPE,))
+    m = cfg.TEST.MULTIPLE
+    if isinstance(m, bool) or not isinstance(m, int) or not 1 <= m <= 16:
+        raise ValueError("TEST.CLIP_METRICS takes TEST.MULTIPLE from 1 to 16 (the pairwise diversity of the copies), got %r" % (m,))
+    return tuple(float(a) for a in alphas)
 
 
 def check_histograms(cfg):

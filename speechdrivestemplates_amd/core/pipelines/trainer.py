@@ -41,8 +41,9 @@ class Trainer(object):
         if not torch.cuda.is_available():
             raise RuntimeError('this engine needs an AMD GPU (no CPU fallback); torch.cuda.is_available() is False')
         torch.cuda.set_device(int(os.environ.get('LOCAL_RANK', self.get_rank() % max(1, torch.cuda.device_count()))))
-        from ...config import check_histograms
+        from ...config import check_clip_metrics, check_histograms
         check_histograms(cfg)  # SYS.HISTOGRAM_INTERVAL without SYS.TENSORBOARD: there is nowhere to write
+        check_clip_metrics(cfg)  # TEST.CLIP_METRICS / TEST.PCK_ALPHAS (a Voice2Pose key)
 
     # -- process-group helpers (trainer.py:29-45) ---------------------------------------------------------
     def get_rank(self):
@@ -480,6 +481,10 @@ class Trainer(object):
         """SYS.DEVICE_FGD and a pipeline that has an epoch-level FGD (Voice2Pose with a pose encoder)"""
         return False
 
+    def uses_clip_metrics(self):
+        """TEST.CLIP_METRICS and a pipeline that has per-clip metrics (Voice2Pose)"""
+        return False
+
     # -- loops (trainer.py:367-427) ----------------------------------------------------------------------
     def train(self, cfg, exp_tag, resume_from=None):
         """``pipeline.train(cfg, exp_tag, args.resume_from)`` as main.py:51 calls it (trainer.py:367).  ``cfg`` is the object
@@ -533,6 +538,9 @@ class Trainer(object):
         device_fgd = self.uses_device_fgd()
         if device_fgd and self.device_fgd() is not None:
             self.device_fgd().reset()
+        clip_metrics = self.uses_clip_metrics()
+        if clip_metrics and self.clip_metrics() is not None:
+            self.clip_metrics().reset()
         for t_step, batch in enumerate(test_dataloader):
             losses, res = self.test_step(batch, t_step + 1, epoch)
             for k, v in losses.items():
@@ -545,6 +553,8 @@ class Trainer(object):
             out.update(self.evaluate_epoch_device())
         elif coll and self.is_master_process():
             out.update(self.evaluate_epoch({k: np.concatenate(v, axis=0) for k, v in coll.items()}))
+        if clip_metrics:  # every rank takes part in the all-gather of the clip tables and gets the whole set's values
+            out.update(self.evaluate_clip_metrics(epoch, tag))
         if self.is_master_process():
             logging.info('[VAL] epoch: %d  val_time: %.1f min  ' % (epoch, (time.time() - tic) / 60) +
                          ''.join('%s: %.5f  ' % (k, float(v)) for k, v in out.items()))

@@ -11,13 +11,14 @@ Deliberate, documented differences from the reference:
   * per-loss scalars are reduced to rank 0 in one packed collective, only on logging steps.
 """
 import logging
+import os
 from collections import OrderedDict
 
 import torch
 from torch import nn
 
 from ... import dp, ops
-from ...config import check_reg_loss
+from ...config import check_clip_metrics, check_reg_loss
 from ...mel import MelSpectrogram
 from ...optim import FlatAdam
 from ..datasets.gesture_dataset import PoseTransforms
@@ -379,6 +380,8 @@ class Voice2Pose(Trainer):
                                                   bool(self.cfg.DATASET.HIERARCHICAL_POSE), True)
         results['poses_pred_batch'], results['poses_gt_batch'] = fin_p, fin_g
         losses['L2_dist'], losses['lip_sync_error_n'] = metrics[0], metrics[1]
+        if self.uses_clip_metrics():  # TEST.CLIP_METRICS: the clips' records go into the table on the device, nothing goes to the host
+            self.clip_metrics(fin_p).add(fin_p, fin_g, batch['clip_index'], m)
         if self.cfg.SYS.DISTRIBUTED:
             dp.reduce_scalars(losses)
         if self.is_master_process():
@@ -458,6 +461,42 @@ class Voice2Pose(Trainer):
                 logging.warning('[VAL] %s: %s' % (key, describe_error(res)))
             out[key] = res['fgd']
         return out
+
+    def uses_clip_metrics(self):
+        return bool(getattr(self.cfg.TEST, 'CLIP_METRICS', False))
+
+    def clip_metrics(self, poses=None):
+        """the table of clip records (created at the first step, which knows the keypoint count and the device); one row per clip of the
+        validation set, addressed by the batch's 'clip_index'"""
+        if getattr(self, '_clip_metrics', None) is None and poses is not None:
+            from ...clip_metrics import ClipMetricsAccumulator
+            ds = getattr(self.test_dataset, 'dataset', self.test_dataset)  # (a Subset keeps the indices of the set it was cut from)
+            self._clip_metrics = ClipMetricsAccumulator(len(ds), poses.shape[3], check_clip_metrics(self.cfg), poses.device,
+                                                        parts=PoseTransforms.part_table())
+        return getattr(self, '_clip_metrics', None)
+
+    def evaluate_clip_metrics(self, epoch, tag):
+        """PCK, part errors, speed ratio, velocity error and diversity over the clips every rank delivered: the ranks' tables are all-gathered
+        and clip by clip the lowest rank that has a record gives it, so every rank reports the same bits.  A clip with a non-finite sum is
+        left out, counted and warned about; so is a clip index outside the table."""
+        from ...clip_metrics import BOOKKEEPING, merge_tables, save_table
+        acc = self.clip_metrics()
+        if acc is None:  # no validation step ran
+            return {}
+        gathered = None
+        if self.cfg.SYS.DISTRIBUTED:
+            gathered = [torch.empty_like(acc.state()) for _ in range(torch.distributed.get_world_size())]
+            torch.distributed.all_gather(gathered, acc.state())  # (the list form: nccl and gloo both have it)
+        res = acc.result(gathered)
+        if res['clips_nonfinite'] or res['index_errors']:
+            logging.warning('[VAL] clip metrics: %d clip(s) left out for a non-finite sum, %d clip index(es) outside the table of %d'
+                            % (res['clips_nonfinite'], res['index_errors'], acc.num_clips))
+        if self.is_master_process() and self.cfg.TEST.SAVE_NPZ and self.base_path is not None:
+            d = os.path.join(self.base_path, 'results')
+            os.makedirs(d, exist_ok=True)
+            tables = [acc.table()] if gathered is None else [g[:acc.num_clips] for g in gathered]
+            save_table('%s/epoch%d-%s-clip_metrics.npz' % (d, epoch, tag), merge_tables([t.cpu().numpy() for t in tables]), acc.alphas)
+        return {k: v for k, v in res.items() if k not in BOOKKEEPING}
 
     def evaluate_epoch(self, results_dict):
         from ...fgd import compute_fgd
