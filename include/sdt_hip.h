@@ -836,6 +836,39 @@ int sdt_clip_metrics_epoch(const void* const* tables, int ranks, int64_t N, cons
                            void* stream);
 int sdt_clip_metrics_sqrt_f64(const double* x, int64_t n, double* y, void* stream);
 
+/*
+ * Whole-recording demo (DEMO.LONG_FORM; speechdrivestemplates_amd/long_demo.py; DESIGN.md section 23 is the contract, long_demo.stitch_model /
+ * smooth_model / report_model are the same operations in numpy; no counterpart in the reference, which runs a demo as one sequence).
+ * Layout, integers only: W frames per window, overlap O with 0 <= 2 O <= W, H = W - O, F >= W frames in all, N = 1 + ceil((F - W) / H)
+ * windows starting at s_i = i H (i < N - 1) and s_{N-1} = F - W; at most three windows cover a frame and they are visited in ascending i.
+ * K in [1, 128], W >= 2; any other size, or an N that does not match, returns SDT_ERR_ARG before any launch.  No allocation, no host
+ * synchronisation, no atomics; every pointer except ``coeffs`` and ``part_sizes`` (host arrays, read during the call) is a device buffer.
+ * Every multiply, add, subtract and divide is rounded on its own (csrc/exact_f64.h).
+ *   gather: out (n, Lw) float32, out[i][j] = audio[offsets[i] + j], 0.0f where that index is outside [0, L).  offsets: n int64 on the device.
+ *   stitch: windows (N, W, 2, K) float64 -> out (F, 2, K).  u_i(t) = min(t - s_i + 1, s_i + W - t), w_i(t) = min(u_i(t), max(O, 1)).  A frame
+ *     that one window covers is that window's value bit for bit; otherwise (w_a x_a + w_b x_b [+ w_c x_c]) / (w_a + w_b [+ w_c]) with the
+ *     products added in ascending window order starting from the first product, and the integer weight sum converted exactly.
+ *   smooth: y(t) = sum over j = -m .. m of coeffs[j + m] * x(clamp(t + j, 0, F - 1)), j ascending, starting from the first product.  x, y:
+ *     (F, 2, K) float64, F >= 1, m in [1, 8], y != x.
+ *   report: parts = K bytes in {0, 1, 2} (body, face, hands), part index p = 0 is "all", p = 1 + byte; part_sizes = 4 int64 {K, body, face,
+ *     hands}; smoothed may be NULL.  out = 40 words of 8 bytes: float64 [0,4) speed[p] and [4,8) jerk[p] of the stitched poses, [8,12) and
+ *     [12,16) the same of the smoothed poses (0.0 without them), [16,20) seam[p]; int64 [20,24) / [24,28) / [28,32) the number of terms behind
+ *     speed / jerk / seam per part, 32 nonfinite (a sum is not finite), 33 F, 34 N, 35 smoothed given, 36 the number of (frame, window pair)
+ *     terms, 37..39 zero.  speed is the mean over (t < F - 1, k in p) of |x(t + 1) - x(t)|, jerk the mean over (t < F - 3, k in p) of
+ *     |((x(t + 3) - 3 x(t + 2)) + 3 x(t + 1)) - x(t)|, seam the mean over the frames with two or more covering windows, their pairs i < j and
+ *     k in p of |x_i(t) - x_j(t)|; a quotient whose divisor is 0 is 0.0.  Within a frame lane k holds keypoint k's term (0 outside the
+ *     part; the pair terms of a keypoint are added in lexicographic (i, j) order first) and the 128 lanes are combined by the xor butterfly
+ *     32, 16, 8, 4, 2, 1 inside each wave, then wave 0 + wave 1; the frames are added in chunks of 64 in ascending order, then the chunk
+ *     partials in order.  work: sdt_long_report_workspace_bytes(F) bytes (-1 for an F outside [1, 2^24]), contents irrelevant.
+ */
+#define SDT_LONG_REPORT_COLS 40
+int sdt_long_windows_gather_f32(const float* audio, int64_t L, const int64_t* offsets, int n, int Lw, float* out, void* stream);
+int sdt_long_stitch_f64(const double* windows, int N, int W, int O, int F, int K, double* out, void* stream);
+int sdt_long_smooth_f64(const double* x, int F, int K, const double* coeffs, int m, double* y, void* stream);
+int64_t sdt_long_report_workspace_bytes(int F);
+int sdt_long_report_f64(const double* windows, const double* stitched, const double* smoothed, const uint8_t* parts, const int64_t* part_sizes,
+                        int N, int W, int O, int F, int K, void* work, void* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

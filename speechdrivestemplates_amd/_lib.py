@@ -184,6 +184,11 @@ SIGNATURES = {
     "sdt_clip_metrics_commit": [_p, _p, _p, _i, _i, _i, _p, _i64, _p],
     "sdt_clip_metrics_epoch": [C.POINTER(C.c_void_p), _i, _i64, C.POINTER(C.c_int64), _i, _p, _p, _p],
     "sdt_clip_metrics_sqrt_f64": [_p, _i64, _p, _p],
+    "sdt_long_windows_gather_f32": [_p, _i64, _p, _i, _i, _p, _p],
+    "sdt_long_stitch_f64": [_p, _i, _i, _i, _i, _i, _p, _p],
+    "sdt_long_smooth_f64": [_p, _i, _i, C.POINTER(C.c_double), _i, _p, _p],
+    "sdt_long_report_workspace_bytes": [_i],  # (returns int64_t: restype set in load())
+    "sdt_long_report_f64": [_p, _p, _p, _p, C.POINTER(C.c_int64), _i, _i, _i, _i, _i, _p, _p, _p],
 }
 F32, BF16 = 0, 1  # enum sdt_dtype
 
@@ -242,6 +247,7 @@ def load():
     lib.sdt_clip_resample_lds_bytes.restype = C.c_int64
     lib.sdt_grad_sumsq_partials.restype = C.c_int64
     lib.sdt_optim_guard_pass_elems.restype = C.c_int64
+    lib.sdt_long_report_workspace_bytes.restype = C.c_int64
     for name in ("threads", "chunk", "buckets", "max_segments"):
         getattr(lib, "sdt_tensor_hist_" + name).restype = C.c_int64
     lib.sdt_conv_dw_group_plan_bytes.argtypes = [_i]

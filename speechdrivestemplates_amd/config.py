@@ -65,7 +65,17 @@ _DEFAULTS = {
              # the master also writes results/epoch<E>-<TAG>-clip_metrics.npz (the table, its column names, the alphas).  False = the loop
              # as it was.  PCK_ALPHAS: one to four thresholds > 0, as fractions of the larger side of the ground truth's bounding box.
              "CLIP_METRICS": False, "PCK_ALPHAS": [0.1, 0.2]},
-    "DEMO": {"MULTIPLE": 1, "NUM_SAMPLES": 1, "CODE_INDEX": None, "CODE_INDEX_B": None, "CODE_PATH": None},
+    "DEMO": {"MULTIPLE": 1, "NUM_SAMPLES": 1, "CODE_INDEX": None, "CODE_INDEX_B": None, "CODE_PATH": None,
+             # extensions (the whole-recording demo, long_demo.LongDemo / csrc/long_demo.hip; Voice2Pose only).
+             # LONG_FORM True = a demo input of F >= DATASET.NUM_FRAMES frames is generated as overlapping windows of NUM_FRAMES frames (the
+             # length the generator was trained at), with one template code for the whole recording, and the windows' final poses are
+             # cross-faded into one sequence on the GPU; shorter inputs, and every input with False, take the single pass as it was.  Set
+             # DATASET.MAX_DEMO_LENGTH None to get the whole file (with a number the crop happens first).
+             # WINDOW_OVERLAP: frames two neighbouring windows share, 0 .. NUM_FRAMES / 2.  LONG_BATCH: windows per forward pass, 1 .. 256.
+             # SMOOTH: None, or [m, d] = a Savitzky-Golay filter of half-width m in 1 .. 8 and degree d in 0 .. 2 m over time on the
+             # stitched poses.  SEGMENT_FRAMES (>= NUM_FRAMES): videos and long images of a long result are written in pieces of at most
+             # this many frames (-part<NN> appended to the file stems when there is more than one).
+             "LONG_FORM": False, "WINDOW_OVERLAP": 16, "LONG_BATCH": 32, "SMOOTH": None, "SEGMENT_FRAMES": 900},
     "SYS": {"OUTPUT_DIR": "output/", "CANVAS_SIZE": (720, 1280), "VISUALIZATION_SCALING": 0.85,
             "VIDEO_FORMAT": ["mp4", "img"], "ASYNC_VIDEO_SAVING": False, "LOG_INTERVAL": 100, "NUM_WORKERS": 8,
             "DISTRIBUTED": False, "WORLD_SIZE": 1, "MASTER_ADDR": "localhost", "MASTER_PORT": 21379,
@@ -233,6 +243,43 @@ def check_clip_metrics(cfg):
     if isinstance(m, bool) or not isinstance(m, int) or not 1 <= m <= 16:
         raise ValueError("TEST.CLIP_METRICS takes TEST.MULTIPLE from 1 to 16 (the pairwise diversity of the copies), got %r" % (m,))
     return tuple(float(a) for a in alphas)
+
+
+def _is_int(v):
+    return isinstance(v, int) and not isinstance(v, bool)
+
+
+def check_long_demo(cfg):
+    """Validate DEMO.LONG_FORM / WINDOW_OVERLAP / LONG_BATCH / SMOOTH / SEGMENT_FRAMES (ValueError names the key).  Returns None with the key
+    off, else {'overlap', 'batch', 'smooth': None or (m, d), 'segment'}."""
+    d, W = cfg.DEMO, cfg.DATASET.NUM_FRAMES
+    on, O, batch, smooth, seg = d.LONG_FORM, d.WINDOW_OVERLAP, d.LONG_BATCH, d.SMOOTH, d.SEGMENT_FRAMES
+    if not isinstance(on, bool):
+        raise ValueError("DEMO.LONG_FORM must be True or False, got %r" % (on,))
+    if not _is_int(O) or O < 0:
+        raise ValueError("DEMO.WINDOW_OVERLAP must be an integer >= 0, got %r" % (O,))
+    if not _is_int(batch) or not 1 <= batch <= 256:
+        raise ValueError("DEMO.LONG_BATCH must be an integer from 1 to 256 (windows per forward pass), got %r" % (batch,))
+    if smooth is not None:
+        if not isinstance(smooth, (list, tuple)) or len(smooth) != 2 or not all(_is_int(v) for v in smooth):
+            raise ValueError("DEMO.SMOOTH must be None or two integers [m, d], got %r" % (smooth,))
+        if not 1 <= smooth[0] <= 8 or not 0 <= smooth[1] <= 2 * smooth[0]:
+            raise ValueError("DEMO.SMOOTH [m, d] needs a half-width m from 1 to 8 and a degree d from 0 to 2 m, got %r" % (smooth,))
+    if not _is_int(seg) or seg < 1:
+        raise ValueError("DEMO.SEGMENT_FRAMES must be a positive integer, got %r" % (seg,))
+    if not on:  # (the bounds that depend on DATASET.NUM_FRAMES hold for a run that uses the keys)
+        return None
+    if cfg.PIPELINE_TYPE != "Voice2Pose":
+        raise ValueError("DEMO.LONG_FORM is a Voice2Pose key (windowed inference from a recording), got PIPELINE_TYPE %r" % (cfg.PIPELINE_TYPE,))
+    if not _is_int(W) or W < 2:
+        raise ValueError("DEMO.LONG_FORM needs windows of DATASET.NUM_FRAMES >= 2 frames, got %r" % (W,))
+    if 2 * O > W:
+        raise ValueError("DEMO.WINDOW_OVERLAP must be at most DATASET.NUM_FRAMES / 2 = %d / 2, got %r" % (W, O))
+    if seg < W:
+        raise ValueError("DEMO.SEGMENT_FRAMES must be at least DATASET.NUM_FRAMES = %d, got %r" % (W, seg))
+    if cfg.VOICE2POSE.GENERATOR.CLIP_CODE.TEST_WITH_GT_CODE:
+        raise ValueError("DEMO.LONG_FORM cannot run with VOICE2POSE.GENERATOR.CLIP_CODE.TEST_WITH_GT_CODE: a demo input has no ground truth")
+    return {'overlap': O, 'batch': batch, 'smooth': None if smooth is None else (smooth[0], smooth[1]), 'segment': seg}
 
 
 def check_histograms(cfg):

@@ -116,7 +116,9 @@ class Voice2PoseModel(nn.Module):
             return c
         return table[torch.randint(table.size(0), (n,), device=dev)]
 
-    def forward(self, batch, dataset, return_loss=True, interpolation_coeff=None):
+    def forward(self, batch, dataset, return_loss=True, interpolation_coeff=None, condition_code=None):
+        """``condition_code`` (n, D): outside training, the codes to condition on in place of ``_eval_code``'s choice (the long-form demo keeps
+        one code over all the windows of a recording)"""
         cfg = self.cfg
         g = cfg.VOICE2POSE.GENERATOR
         dev = self._device()
@@ -131,8 +133,9 @@ class Voice2PoseModel(nn.Module):
             if self.training:
                 condition_code, kl, kl_valid = ops.CodeGatherKLFn.apply(self._code_table(dev), clip_indices, g.LAMBDA_CLIP_KL)
             else:
-                condition_code = self._eval_code(batch, audio.shape[0], dev, poses_gt, dataset, speaker, interpolation_coeff,
-                                                 return_loss)
+                if condition_code is None:
+                    condition_code = self._eval_code(batch, audio.shape[0], dev, poses_gt, dataset, speaker, interpolation_coeff,
+                                                     return_loss)
                 if return_loss:
                     ar = torch.arange(condition_code.shape[0], device=dev)
                     _, kl, kl_valid = ops.CodeGatherKLFn.apply(condition_code.detach().contiguous(), ar, g.LAMBDA_CLIP_KL, True)
@@ -407,14 +410,38 @@ class Voice2Pose(Trainer):
         reference's 24 s demo limit); returns de-normalised global poses (1, T, 2, 121) in float64."""
         self.model.eval()
         self.apply_knobs()
-        results = self.model(batch, self.test_dataset, return_loss=False, interpolation_coeff=interpolation_coeff)
-        results['poses_pred_batch'] = self.test_dataset.get_final_results(results['poses_pred_batch'].detach(), batch['speaker_stat'])
+        long_form = self.cfg.DEMO.LONG_FORM and int(batch['num_frames'][0]) >= self.cfg.DATASET.NUM_FRAMES
+        if long_form:  # DEMO.LONG_FORM: windows of the training length, stitched / smoothed / reported on the GPU (DESIGN.md section 23)
+            results = self.long_demo().run(batch, interpolation_coeff)
+        else:
+            results = self.model(batch, self.test_dataset, return_loss=False, interpolation_coeff=interpolation_coeff)
+            results['poses_pred_batch'] = self.test_dataset.get_final_results(results['poses_pred_batch'].detach(), batch['speaker_stat'])
         if self.is_master_process() and self.cfg.TEST.SAVE_NPZ and self.base_path is not None:
             self.save_results('DEMO', t_step, epoch, self.base_path,
                               {k: v.detach().cpu().numpy() for k, v in results.items() if torch.is_tensor(v)}, extra_id=extra_id)
         if self.is_master_process() and self.cfg.TEST.SAVE_VIDEO and self.rendering() and self.base_path is not None:
-            self.write_demo_video(results['poses_pred_batch'][0], t_step, epoch, batch['audio'], extra_id)
+            if long_form:
+                self.write_long_demo_videos(results['poses_pred_batch'][0], t_step, epoch, batch['audio'], extra_id)
+            else:
+                self.write_demo_video(results['poses_pred_batch'][0], t_step, epoch, batch['audio'], extra_id)
         return results
+
+    def long_demo(self):
+        """the long-form runner (created by the first long input)"""
+        if getattr(self, '_long_demo', None) is None:
+            from ...long_demo import LongDemo
+            self._long_demo = LongDemo(self)
+        return self._long_demo
+
+    def write_long_demo_videos(self, pred, t_step, epoch, audio, extra_id=None):
+        """``write_demo_video`` per segment of at most DEMO.SEGMENT_FRAMES frames with the matching audio slice; one segment keeps the usual
+        file names, several get -part<NN> appended"""
+        from ...long_demo import segments
+        segs = segments(int(pred.shape[0]), self.cfg.DEMO.SEGMENT_FRAMES)
+        sr, fps = self.cfg.DATASET.AUDIO_SR, self.cfg.DATASET.FPS
+        for j, (a, b) in enumerate(segs):
+            part = extra_id if len(segs) == 1 else ('part%02d' % j if extra_id is None else '%d-part%02d' % (extra_id, j))
+            self.write_demo_video(pred[a:b], t_step, epoch, audio[:, a * sr // fps:b * sr // fps], part)
 
     def draw_figure_epoch(self):
         """the clip-code table (learned, or the external codes of sdt_vae) projected on its two principal axes (voice2pose.py:479-510)"""

@@ -61,6 +61,8 @@ def _audio_np(audio):
 
 
 def _stem(epoch, tag, step, extra_id):
+    if isinstance(extra_id, str):  # (a long demo's segment: 'part01', or '<id>-part01')
+        return 'epoch%d-%s-step%s-%s' % (epoch, tag, step, extra_id)
     return 'epoch%d-%s-step%s' % (epoch, tag, step) if extra_id is None else 'epoch%d-%s-step%s-%d' % (epoch, tag, step, extra_id)
 
 
