@@ -869,6 +869,53 @@ int64_t sdt_long_report_workspace_bytes(int F);
 int sdt_long_report_f64(const double* windows, const double* stitched, const double* smoothed, const uint8_t* parts, const int64_t* part_sizes,
                         int N, int W, int O, int F, int K, void* work, void* out, void* stream);
 
+/*
+ * Speech-gesture synchrony (TEST.SYNC_METRICS; speechdrivestemplates_amd/sync_metrics.py; DESIGN.md section 24 is the contract, sync_metrics.
+ * onsets_model / beats_model / match_model / sync_model / epoch_model are the same operations in numpy; no counterpart in the reference).
+ * Times are integers in ticks of 1/300 s at 16000 samples/s and 15 frames/s: an audio hop of 160 samples is 3 ticks, a pose frame 20.  Every
+ * multiply, add, subtract and divide is rounded on its own (csrc/exact_f64.h); no floating-point atomics, no allocation, no host
+ * synchronisation; every pointer except ``tables`` (a host array, read during the call) is a device buffer; every size is checked before
+ * the launch (K in [1, 128], tol in [1, 150], T in [1, 2^24], L in [0, 160 * 2^28]; otherwise SDT_ERR_ARG).
+ *   onsets: audio (B, L) float32.  Nf = L / 160 frames, frame n covers samples [160 n, 160 n + 320), 0.0 at or past L.  e[n] = sqrt(sum x^2):
+ *     lane l of a wave adds the squares of samples l, l + 64, .., l + 256 in that order (the first product starts the sum), then the xor
+ *     butterfly 32 .. 1.  o[0] = 0, o[n] = e[n] - e[n-1] where that is > 0, else 0.  Frame 1 <= n <= Nf - 2 is a candidate if o[n] > o[n-1],
+ *     o[n] >= o[n+1], o[n] > delta * mean (the sum of o over [n-15, n+15] clipped to the clip, ascending from +0.0, divided by the count) and
+ *     o[n] > floor_frac * max e.  Candidates are accepted left to right; one fewer than 8 frames after the last accepted one is dropped.
+ *     ticks (B, cap) int32: 3 n + 3 of the accepted frames, ascending; cap >= sdt_sync_onset_capacity(L) = Nf / 8 + 1.  info (B, 2) int64:
+ *     the number of onsets, and 1 if an e[n] is not finite.  work: e (B, Nf) then o (B, Nf) float64.
+ *   rows: poses (R, T, 2, K) float64, parts K bytes in {0, 1, 2}; part index p = 0 is "all", p = 1 + byte.  Row r belongs to clip r % B of
+ *     ticks / info.  s_p[t] (t < T - 1) = sum over k in p of |x(t+1) - x(t)|, formed as sdt_clip_metrics_rows_f64 forms speed_pred.  t in
+ *     [1, T - 3] is a beat of part p if s[t] > s[t-1], s[t] >= s[t+1] and s[t] > gamma * (sum of s in order from +0.0) / (T - 1); its tick is
+ *     20 t + 10, d = min(distance to the nearest onset tick, 150) (150 without onsets).  A row record is SDT_SYNC_ROW_COLS words of 8 bytes:
+ *     float64 [0,4) align[p] = sum of gauss[d] in beat order from +0.0 (gauss: 151 float64); int64 [4,8) beats[p], [8,12) hits[p] (d <= tol),
+ *     [12,16) dsum[p], [16,20) covered[p] (onsets with a beat of part p within tol), 20 onsets, 21 nonfinite (a speed sum or an e[n] is not
+ *     finite), 22 T, 23 zero.  work: s (R, T - 1, 4) float64, then the beat flags (R, 4, T) bytes.
+ *   sdt_sync_workspace_bytes(B, L, R, T): bytes of the larger of the two work buffers (-1 for a size outside the ranges).
+ *   commit: clip b's record = the sum over its m copies (rows j * B + b, j ascending) of the prediction's and the ground truth's row records
+ *     (rows_gt may be NULL: zeros), into row clip_index[b] of table, (N + 1) x SDT_SYNC_COLS words; row N is the header, whose word 0 counts
+ *     the indices outside [0, N).  A clip record: float64 [0,4) align_pred[p], [4,8) align_gt[p]; int64 [8,24) beats, hits, dsum, covered of
+ *     the prediction (4 words each), [24,40) of the ground truth, 40 onsets (summed over the copies), 41 seen, 42 copies, 43 nonfinite, 44 T,
+ *     45 Nf, 46..47 zero.
+ *   epoch: as sdt_clip_metrics_epoch: the lowest rank with seen set gives clip n's record, nonfinite records are left out and counted,
+ *     chunks of 64 clips in index order, then the chunk partials in order; work: ceil(N / 64) * SDT_SYNC_COLS words.  out is
+ *     SDT_SYNC_OUT_COLS words: float64 pairs {all, hands} 0 precision = hits / beats, 2 precision_gt, 4 recall = covered / onsets, 6 recall_gt,
+ *     8 offset_ms = dsum * (1000 / 300) / beats, 10 beat_align = align / beats, 12 beat_align_gt, 14 beats * 15 / sum(copies * T), 16 the
+ *     same of the ground truth, 18 onsets * 100 / sum(copies * Nf), 19 zero; int64 20 clips with a record, 21 of them left out as nonfinite,
+ *     22 index errors of all tables, 23 zero.  A quotient whose divisor is 0 is 0.0.
+ */
+#define SDT_SYNC_ROW_COLS 24
+#define SDT_SYNC_COLS 48
+#define SDT_SYNC_OUT_COLS 24
+int64_t sdt_sync_onset_capacity(int64_t L);
+int64_t sdt_sync_workspace_bytes(int B, int64_t L, int R, int T);
+int sdt_sync_onsets_f64(const float* audio, int B, int64_t L, double delta, double floor_frac, void* work, int32_t* ticks, int64_t cap,
+                        int64_t* info, void* stream);
+int sdt_sync_rows_f64(const double* poses, const uint8_t* parts, int R, int T, int K, int B, const int32_t* ticks, int64_t cap,
+                      const int64_t* info, const double* gauss, int tol, double gamma, void* work, void* rows, void* stream);
+int sdt_sync_commit(const void* rows_pred, const void* rows_gt, const int64_t* clip_index, int B, int m, int T, int64_t L, void* table, int64_t N,
+                    void* stream);
+int sdt_sync_epoch(const void* const* tables, int ranks, int64_t N, void* work, void* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -189,6 +189,12 @@ SIGNATURES = {
     "sdt_long_smooth_f64": [_p, _i, _i, C.POINTER(C.c_double), _i, _p, _p],
     "sdt_long_report_workspace_bytes": [_i],  # (returns int64_t: restype set in load())
     "sdt_long_report_f64": [_p, _p, _p, _p, C.POINTER(C.c_int64), _i, _i, _i, _i, _i, _p, _p, _p],
+    "sdt_sync_onset_capacity": [_i64],  # (the two size functions return int64_t: restype set in load())
+    "sdt_sync_workspace_bytes": [_i, _i64, _i, _i],
+    "sdt_sync_onsets_f64": [_p, _i, _i64, C.c_double, C.c_double, _p, _p, _i64, _p, _p],
+    "sdt_sync_rows_f64": [_p, _p, _i, _i, _i, _i, _p, _i64, _p, _p, _i, C.c_double, _p, _p, _p],
+    "sdt_sync_commit": [_p, _p, _p, _i, _i, _i, _i64, _p, _i64, _p],
+    "sdt_sync_epoch": [C.POINTER(C.c_void_p), _i, _i64, _p, _p, _p],
 }
 F32, BF16 = 0, 1  # enum sdt_dtype
 
@@ -248,6 +254,8 @@ def load():
     lib.sdt_grad_sumsq_partials.restype = C.c_int64
     lib.sdt_optim_guard_pass_elems.restype = C.c_int64
     lib.sdt_long_report_workspace_bytes.restype = C.c_int64
+    lib.sdt_sync_onset_capacity.restype = C.c_int64
+    lib.sdt_sync_workspace_bytes.restype = C.c_int64
     for name in ("threads", "chunk", "buckets", "max_segments"):
         getattr(lib, "sdt_tensor_hist_" + name).restype = C.c_int64
     lib.sdt_conv_dw_group_plan_bytes.argtypes = [_i]

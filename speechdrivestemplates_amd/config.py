@@ -4,6 +4,7 @@ a ~60-line attribute-access dict with the four methods the reference calls (merg
 merge_from_list, freeze, clone)."""
 import ast
 import copy
+import math
 
 import yaml
 
@@ -64,7 +65,17 @@ _DEFAULTS = {
              # and clips_nonfinite to their values: over the tables of ALL ranks (one all-gather), the same bits on every rank.  With SAVE_NPZ
              # the master also writes results/epoch<E>-<TAG>-clip_metrics.npz (the table, its column names, the alphas).  False = the loop
              # as it was.  PCK_ALPHAS: one to four thresholds > 0, as fractions of the larger side of the ground truth's bounding box.
-             "CLIP_METRICS": False, "PCK_ALPHAS": [0.1, 0.2]},
+             "CLIP_METRICS": False, "PCK_ALPHAS": [0.1, 0.2],
+             # extensions (speech-gesture synchrony, sync_metrics.SyncAccumulator / csrc/sync_metrics.hip; Voice2Pose only;
+             # needs DATASET.AUDIO_SR 16000 and DATASET.FPS 15).  SYNC_METRICS True = every test_step also detects the audio onsets of its
+             # clips and the motion beats of the final poses (prediction and ground truth, per body part) on the GPU and commits how they line
+             # up to a table, and validate() / test() add sync_precision, sync_recall, sync_offset_ms, beat_align, beats_per_s (each also
+             # _gt = what the real motion achieves on the same audio, and _hands), onsets_per_s and sync_clips_nonfinite to their values: over
+             # the tables of ALL ranks, the same bits on every rank.  With SAVE_NPZ the master also writes
+             # results/epoch<E>-<TAG>-sync_metrics.npz.  With DEMO.LONG_FORM the long demo reports the same counts over the whole recording.
+             # SYNC_TOLERANCE: a beat within this many seconds of an onset is a hit (floor(300 tol + 0.5) ticks of 1/300 s, 1 .. 150).
+             # SYNC_SIGMA: the width in seconds of the Gaussian that beat_align weighs a beat's distance with.  False = the loop as it was.
+             "SYNC_METRICS": False, "SYNC_TOLERANCE": 0.1, "SYNC_SIGMA": 0.1},
     "DEMO": {"MULTIPLE": 1, "NUM_SAMPLES": 1, "CODE_INDEX": None, "CODE_INDEX_B": None, "CODE_PATH": None,
              # extensions (the whole-recording demo, long_demo.LongDemo / csrc/long_demo.hip; Voice2Pose only).
              # LONG_FORM True = a demo input of F >= DATASET.NUM_FRAMES frames is generated as overlapping windows of NUM_FRAMES frames (the
@@ -247,6 +258,35 @@ def check_clip_metrics(cfg):
 
 def _is_int(v):
     return isinstance(v, int) and not isinstance(v, bool)
+
+
+def check_sync_metrics(cfg):
+    """Validate TEST.SYNC_METRICS / SYNC_TOLERANCE / SYNC_SIGMA (ValueError names the key).  Returns None with the key off, else
+    {'tol_ticks', 'sigma'}."""
+    on, tol, sigma = cfg.TEST.SYNC_METRICS, cfg.TEST.SYNC_TOLERANCE, cfg.TEST.SYNC_SIGMA
+    if not isinstance(on, bool):
+        raise ValueError("TEST.SYNC_METRICS must be True or False, got %r" % (on,))
+    if not _is_number(tol):
+        raise ValueError("TEST.SYNC_TOLERANCE must be a finite number of seconds, got %r" % (tol,))
+    ticks = int(math.floor(300 * float(tol) + 0.5))
+    if not 1 <= ticks <= 150:
+        raise ValueError("TEST.SYNC_TOLERANCE of %r s is %d ticks of 1/300 s, outside 1 .. 150 (0.5 s)" % (tol, ticks))
+    if not _is_number(sigma) or not sigma > 0:
+        raise ValueError("TEST.SYNC_SIGMA must be a finite number of seconds > 0, got %r" % (sigma,))
+    if not on:
+        return None
+    if cfg.PIPELINE_TYPE != "Voice2Pose":
+        raise ValueError("TEST.SYNC_METRICS is a Voice2Pose key (audio onsets against the beats of predicted gestures), got PIPELINE_TYPE %r"
+                         % (cfg.PIPELINE_TYPE,))
+    if cfg.DATASET.AUDIO_SR != 16000:
+        raise ValueError("TEST.SYNC_METRICS needs DATASET.AUDIO_SR 16000 (an audio hop of 160 samples is 3 ticks of 1/300 s), got %r"
+                         % (cfg.DATASET.AUDIO_SR,))
+    if cfg.DATASET.FPS != 15:
+        raise ValueError("TEST.SYNC_METRICS needs DATASET.FPS 15 (a pose frame is 20 ticks of 1/300 s), got %r" % (cfg.DATASET.FPS,))
+    m = cfg.TEST.MULTIPLE
+    if isinstance(m, bool) or not isinstance(m, int) or not 1 <= m <= 16:
+        raise ValueError("TEST.SYNC_METRICS takes TEST.MULTIPLE from 1 to 16, got %r" % (m,))
+    return {'tol_ticks': ticks, 'sigma': float(sigma)}
 
 
 def check_long_demo(cfg):

@@ -385,6 +385,8 @@ class Voice2Pose(Trainer):
         losses['L2_dist'], losses['lip_sync_error_n'] = metrics[0], metrics[1]
         if self.uses_clip_metrics():  # TEST.CLIP_METRICS: the clips' records go into the table on the device, nothing goes to the host
             self.clip_metrics(fin_p).add(fin_p, fin_g, batch['clip_index'], m)
+        if self.uses_sync_metrics():  # TEST.SYNC_METRICS: audio onsets against the beats of both pose tensors, all on the device
+            self.sync_metrics(fin_p).add(fin_p, fin_g, batch['audio'].to(dev, non_blocking=True).float(), batch['clip_index'], m)
         if self.cfg.SYS.DISTRIBUTED:
             dp.reduce_scalars(losses)
         if self.is_master_process():
@@ -523,6 +525,43 @@ class Voice2Pose(Trainer):
             os.makedirs(d, exist_ok=True)
             tables = [acc.table()] if gathered is None else [g[:acc.num_clips] for g in gathered]
             save_table('%s/epoch%d-%s-clip_metrics.npz' % (d, epoch, tag), merge_tables([t.cpu().numpy() for t in tables]), acc.alphas)
+        return {k: v for k, v in res.items() if k not in BOOKKEEPING}
+
+    def uses_sync_metrics(self):
+        return bool(getattr(self.cfg.TEST, 'SYNC_METRICS', False))
+
+    def sync_metrics(self, poses=None):
+        """the table of synchrony records (created at the first step, which knows the keypoint count and the device); one row per clip of
+        the validation set, addressed by the batch's 'clip_index'"""
+        if getattr(self, '_sync_metrics', None) is None and poses is not None:
+            from ...config import check_sync_metrics
+            from ...sync_metrics import SyncAccumulator
+            opts = check_sync_metrics(self.cfg)
+            ds = getattr(self.test_dataset, 'dataset', self.test_dataset)  # (a Subset keeps the indices of the set it was cut from)
+            self._sync_metrics = SyncAccumulator(len(ds), poses.shape[3], opts['tol_ticks'], opts['sigma'], poses.device,
+                                                 parts=PoseTransforms.part_table())
+        return getattr(self, '_sync_metrics', None)
+
+    def evaluate_sync_metrics(self, epoch, tag):
+        """precision, recall, offset and alignment of the beats against the audio onsets over the clips every rank delivered, merged as
+        ``evaluate_clip_metrics`` merges its tables.  A clip with a non-finite sum is left out, counted and warned about."""
+        from ...sync_metrics import BOOKKEEPING, merge_tables, save_table
+        acc = self.sync_metrics()
+        if acc is None:  # no validation step ran
+            return {}
+        gathered = None
+        if self.cfg.SYS.DISTRIBUTED:
+            gathered = [torch.empty_like(acc.state()) for _ in range(torch.distributed.get_world_size())]
+            torch.distributed.all_gather(gathered, acc.state())  # (the list form: nccl and gloo both have it)
+        res = acc.result(gathered)
+        if res['sync_clips_nonfinite'] or res['sync_index_errors']:
+            logging.warning('[VAL] sync metrics: %d clip(s) left out for a non-finite sum, %d clip index(es) outside the table of %d'
+                            % (res['sync_clips_nonfinite'], res['sync_index_errors'], acc.num_clips))
+        if self.is_master_process() and self.cfg.TEST.SAVE_NPZ and self.base_path is not None:
+            d = os.path.join(self.base_path, 'results')
+            os.makedirs(d, exist_ok=True)
+            tables = [acc.table()] if gathered is None else [g[:acc.num_clips] for g in gathered]
+            save_table('%s/epoch%d-%s-sync_metrics.npz' % (d, epoch, tag), merge_tables([t.cpu().numpy() for t in tables]), acc.tol, acc.sigma)
         return {k: v for k, v in res.items() if k not in BOOKKEEPING}
 
     def evaluate_epoch(self, results_dict):

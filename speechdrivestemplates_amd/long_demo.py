@@ -341,6 +341,8 @@ class LongDemo:
         self.Lw = parse_audio_length(cfg.DATASET.AUDIO_LENGTH, self.sr, self.fps)[0]
         self.parts = PoseTransforms.part_table()
         self.table = None if self.opts['smooth'] is None else savgol_table(*self.opts['smooth'])
+        from .config import check_sync_metrics
+        self.sync = check_sync_metrics(cfg)  # TEST.SYNC_METRICS: None, or the tolerance in ticks and sigma
 
     def _code(self, dev, interpolation_coeff):
         """one template code (1, D) for the whole recording: DEMO.CODE_INDEX (interpolated towards CODE_INDEX_B by the step's coefficient), or
@@ -407,8 +409,17 @@ class LongDemo:
         final = stitched if self.table is None else smooth(stitched, self.table)
         words = report(windows, stitched, None if self.table is None else final, O, self.parts).cpu()
         logging.info('[DEMO] long form: ' + describe(words.numpy()))
-        return {'poses_pred_batch': final.unsqueeze(0), 'condition_code': code, 'poses_windows': windows,
-                'window_starts': torch.tensor(starts, dtype=torch.int64), 'poses_stitched': stitched.unsqueeze(0), 'long_report': words}
+        out = {'poses_pred_batch': final.unsqueeze(0), 'condition_code': code, 'poses_windows': windows,
+               'window_starts': torch.tensor(starts, dtype=torch.int64), 'poses_stitched': stitched.unsqueeze(0), 'long_report': words}
+        if self.sync is not None:  # audio onsets against the beats of the whole recording: one row, T = F, no ground truth
+            from . import sync_metrics as sm
+            audio = batch['audio'].to(final.device, non_blocking=True)[0].float()
+            which = [('final', final)] + ([] if self.table is None else [('stitched', stitched)])
+            out['sync_report'] = torch.stack([sm.recording_report(x, audio, self.sync['tol_ticks'], self.sync['sigma'], self.parts)
+                                              for _, x in which]).cpu()
+            for (name, _), rec in zip(which, out['sync_report'].numpy()):
+                logging.info('[DEMO] sync: %s poses: ' % name + sm.describe_row(rec, audio.numel() // sm.HOP))
+        return out
 
 
 OUT_KEYS = ('poses_stitched', 'poses_pred_batch', 'window_starts', 'long_report')  # entries of the command line's OUT.npz
