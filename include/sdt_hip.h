@@ -916,6 +916,46 @@ int sdt_sync_commit(const void* rows_pred, const void* rows_gt, const int64_t* c
                     void* stream);
 int sdt_sync_epoch(const void* const* tables, int ranks, int64_t N, void* work, void* out, void* stream);
 
+/*
+ * Audio augmentation inside the train step (TRAIN.AUGMENT; speechdrivestemplates_amd/augment.py; DESIGN.md section 25 is the contract, augment.
+ * philox4x32 / sumsq_model / clip_params_model / audio_model / mel_mask_model are the same operations in numpy; no counterpart in the
+ * reference).  Random words are Philox4x32-10 (multipliers D2511F53 / CD9E8D57, Weyl constants 9E3779B9 / BB67AE85) with the key (seed low
+ * 32 bits, seed high 32 bits) and the counter (block j, purpose, clip_index[b] low 32 bits, step[0] low 32 bits): nothing depends on the
+ * clip's row, on B or on the rank.  Purpose 0: block 0 gives the clip's parameters from its words w0 .. w3, blocks 1 .. nf the frequency
+ * masks, blocks 5 .. 4 + nt the time masks.  Purpose 1: noise sample n takes block n >> 1, words 2 (n & 1) and 2 (n & 1) + 1.  No
+ * transcendental function, no allocation, no host synchronisation, no atomics; clip_index (B,) and step (1,) are int64 device buffers read
+ * by the kernels, so a captured graph follows them; every size is checked before the launch (B in [1, 65535], L in [1, 2^24]; otherwise
+ * SDT_ERR_ARG).  Every float64 multiply, add and divide is rounded on its own (csrc/exact_f64.h).
+ *   sumsq: audio (B, L) float32 -> ss (B,) float64, the sum of the squares (each exact in float64) in this order: chunk c covers samples
+ *     [1024 c, 1024 c + 1024); thread t of 256 adds the squares of samples 1024 c + t + 256 k, k = 0 .. 3, from +0.0 (+0.0 at or past L);
+ *     the xor butterfly 32, 16, 8, 4, 2, 1 inside each of the four waves; ((wave 0 + wave 1) + wave 2) + wave 3 is the chunk's partial.
+ *     Then lane l adds the partials l, l + 64, .. from +0.0 and the same butterfly follows.  work: sdt_augment_workspace_bytes(B, L) bytes
+ *     (-1 for a size outside the ranges), contents irrelevant.
+ *   audio: out (B, L) float32, out != audio.  Per clip, from block 0: ig = w0 >> 24, g = gain_table[ig] (256 float32), negated when
+ *     polarity and w3 & 1; is = w1 >> 24, a = snr_table[is] (256 float64); s = (w2 mod (2 max_shift + 1)) - max_shift; the noise is on iff
+ *     (w3 >> 8) < noise_prob24 (0 .. 2^24); sigma = sqrt(ss[b] / L) * a with the noise on, else 0.0.  x_s[n] = audio[b][n - s] inside
+ *     [0, L), else +0.0.  z[n] = (h0 + h1 + h2 + h3 - 131070) * 0x1.bb67ae86627e7p-16 over the four 16-bit halves of the sample's two words
+ *     (the integer converts exactly).  out[b][n] = float32(float64(g) * (float64(x_s[n]) + sigma * z[n])) with the noise on and
+ *     float32(float64(g) * float64(x_s[n])) with it off (no noise term is formed, so a -0.0 keeps its sign).  One read and one write of the
+ *     audio; the elements before the first 16-byte boundary of an output row and the last L' mod 4 are written one by one, the rest by
+ *     16-byte stores; no read or write outside a row.  rec (B, SDT_AUGMENT_REC_COLS) words of 8 bytes: int64 0 ig, 1 is, 2 s, 3 polarity,
+ *     4 noise on, float64 5 sigma, 6 ss, int64 7 nonfinite (ss is not finite: a NaN or inf sits in that clip, and only that clip's output
+ *     is affected), 8 .. 31 zero.
+ *   mel mask: mel (B, M, F) float32, in place.  Mask i of a dimension of size D (M for a frequency band, F for a time span) and largest
+ *     width w: width = w0 mod (w + 1), clipped to D; start = w1 mod (D - width + 1); the rectangle spans the whole other dimension and is
+ *     set to +0.0; elements outside every rectangle are neither read nor written.  The moduli are biased by at most (w + 1) 2^-32 resp.
+ *     D 2^-32.  rec words 8 + 2 i, 9 + 2 i: start, width of frequency mask i; 16 + 2 i, 17 + 2 i: of time mask i (0, 0 for i >= n);
+ *     24 nf, 25 nt.  Words 0 .. 7 and 26 .. 31 are left as they are.
+ */
+#define SDT_AUGMENT_REC_COLS 32
+int64_t sdt_augment_workspace_bytes(int B, int64_t L);
+int sdt_augment_sumsq_f64(const float* audio, int B, int64_t L, void* work, double* ss, void* stream);
+int sdt_augment_audio_f32(const float* audio, int B, int64_t L, const int64_t* clip_index, const int64_t* step, const double* ss, uint64_t seed,
+                          int64_t max_shift, int64_t noise_prob24, int polarity, const float* gain_table, const double* snr_table, void* rec,
+                          float* out, void* stream);
+int sdt_augment_mel_mask_f32(float* mel, int B, int M, int F, const int64_t* clip_index, const int64_t* step, uint64_t seed, int nf, int wf, int nt,
+                             int wt, void* rec, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -195,6 +195,10 @@ SIGNATURES = {
     "sdt_sync_rows_f64": [_p, _p, _i, _i, _i, _i, _p, _i64, _p, _p, _i, C.c_double, _p, _p, _p],
     "sdt_sync_commit": [_p, _p, _p, _i, _i, _i, _i64, _p, _i64, _p],
     "sdt_sync_epoch": [C.POINTER(C.c_void_p), _i, _i64, _p, _p, _p],
+    "sdt_augment_workspace_bytes": [_i, _i64],  # (returns int64_t: restype set in load())
+    "sdt_augment_sumsq_f64": [_p, _i, _i64, _p, _p, _p],
+    "sdt_augment_audio_f32": [_p, _i, _i64, _p, _p, _p, C.c_uint64, _i64, _i64, _i, _p, _p, _p, _p, _p],
+    "sdt_augment_mel_mask_f32": [_p, _i, _i, _i, _p, _p, C.c_uint64, _i, _i, _i, _i, _p, _p],
 }
 F32, BF16 = 0, 1  # enum sdt_dtype
 
@@ -256,6 +260,7 @@ def load():
     lib.sdt_long_report_workspace_bytes.restype = C.c_int64
     lib.sdt_sync_onset_capacity.restype = C.c_int64
     lib.sdt_sync_workspace_bytes.restype = C.c_int64
+    lib.sdt_augment_workspace_bytes.restype = C.c_int64
     for name in ("threads", "chunk", "buckets", "max_segments"):
         getattr(lib, "sdt_tensor_hist_" + name).restype = C.c_int64
     lib.sdt_conv_dw_group_plan_bytes.argtypes = [_i]

@@ -56,7 +56,20 @@ _DEFAULTS = {
               # EMA_DECAY: d in (0, 1) keeps ema = d * ema + (1 - d) * p of the generator-side parameters (optimizerG, optimizerClipCode;
               # pose2pose's optimiser), updated after every applied step and saved as 'model_ema_state_dict'.  The discriminator and the
               # BatchNorm running statistics (buffers) are not averaged.
-              "GRAD_CLIP_NORM": None, "SKIP_NONFINITE_STEP": False, "EMA_DECAY": None},
+              "GRAD_CLIP_NORM": None, "SKIP_NONFINITE_STEP": False, "EMA_DECAY": None,
+              # extension (audio augmentation inside the train step, augment.Augmenter / csrc/augment.hip; Voice2Pose
+              # only; every key off by default = the step as it was, no kernel launched).  With ENABLE the training forward pass hands the
+              # batch's audio through one GPU pass before the mel front end and zeroes bands and spans of the power mel behind it; evaluation
+              # and the demo hear clean audio.  Everything random is a Philox4x32-10 word of (SEED, global step, clip index): the same on any
+              # number of ranks, at any batch size and after a resume.
+              # SEED: integer in [0, 2^64), the Philox key.  GAIN_DB G in [0, 40]: a per-clip gain, uniform over 256 levels in [-G, +G] dB.
+              # NOISE_SNR_DB: None, or [lo, hi] with -20 <= lo <= hi <= 80: white noise at a per-clip SNR (256 levels in [lo, hi] dB) against
+              # the clip's own RMS; NOISE_PROB in [0, 1]: the share of clips that get it.  SHIFT_MS in [0, 500]: the audio moves against the
+              # poses by a uniform whole number of samples in +-floor(SHIFT_MS * AUDIO_SR / 1000), zero-filled.  POLARITY: a random sign
+              # flip per clip.  MEL_FREQ_MASKS [n, w]: n in 0 .. 4 bands of 0 .. w (at most 40) mel bins set to 0; MEL_TIME_MASKS [n, w]:
+              # n in 0 .. 4 spans of 0 .. w (at most 100) mel columns set to 0.
+              "AUGMENT": {"ENABLE": False, "SEED": 0, "GAIN_DB": 0.0, "NOISE_SNR_DB": None, "NOISE_PROB": 1.0, "SHIFT_MS": 0.0,
+                          "POLARITY": False, "MEL_FREQ_MASKS": [0, 0], "MEL_TIME_MASKS": [0, 0]}},
     "TEST": {"BATCH_SIZE": 32, "NUM_RESULT_SAMPLE": 8, "SAVE_VIDEO": True, "SAVE_NPZ": True, "MULTIPLE": 1,
              # extensions (per-clip validation metrics, clip_metrics.ClipMetricsAccumulator / csrc/clip_metrics.hip; DESIGN.md section 22;
              # Voice2Pose only).  CLIP_METRICS True = every test_step also commits its clips' records (keypoint-distance, PCK-hit, speed,
@@ -287,6 +300,63 @@ def check_sync_metrics(cfg):
     if isinstance(m, bool) or not isinstance(m, int) or not 1 <= m <= 16:
         raise ValueError("TEST.SYNC_METRICS takes TEST.MULTIPLE from 1 to 16, got %r" % (m,))
     return {'tol_ticks': ticks, 'sigma': float(sigma)}
+
+
+def check_augment(cfg):
+    """Validate TRAIN.AUGMENT (ValueError names the key).  With ENABLE off the other keys are checked for their type only and None is
+    returned; otherwise their ranges too, and {'seed', 'gain_db', 'snr': None or (lo, hi), 'noise_prob', 'shift_ms', 'shift': the largest
+    shift in samples, 'polarity', 'freq_masks': (n, w), 'time_masks': (n, w)} comes back as Python values."""
+    a, pre = cfg.TRAIN.AUGMENT, "TRAIN.AUGMENT."
+    on, seed, gain, snr, prob, shift, pol = a.ENABLE, a.SEED, a.GAIN_DB, a.NOISE_SNR_DB, a.NOISE_PROB, a.SHIFT_MS, a.POLARITY
+    if not isinstance(on, bool):
+        raise ValueError(pre + "ENABLE must be True or False, got %r" % (on,))
+    if not _is_int(seed):
+        raise ValueError(pre + "SEED must be an integer, got %r" % (seed,))
+    if not _is_number(gain):
+        raise ValueError(pre + "GAIN_DB must be a finite number, got %r" % (gain,))
+    if snr is not None and (not isinstance(snr, (list, tuple)) or len(snr) != 2 or not all(_is_number(v) for v in snr)):
+        raise ValueError(pre + "NOISE_SNR_DB must be None or two finite numbers [lo, hi], got %r" % (snr,))
+    if not _is_number(prob):
+        raise ValueError(pre + "NOISE_PROB must be a finite number, got %r" % (prob,))
+    if not _is_number(shift):
+        raise ValueError(pre + "SHIFT_MS must be a finite number, got %r" % (shift,))
+    if not isinstance(pol, bool):
+        raise ValueError(pre + "POLARITY must be True or False, got %r" % (pol,))
+    masks = {}
+    for key, widest in (("MEL_FREQ_MASKS", 40), ("MEL_TIME_MASKS", 100)):
+        v = a[key]
+        if not isinstance(v, (list, tuple)) or len(v) != 2 or not all(_is_int(x) for x in v):
+            raise ValueError(pre + key + " must be two integers [n, w], got %r" % (v,))
+        masks[key] = (int(v[0]), int(v[1]), widest)
+    if not on:
+        return None
+    if cfg.PIPELINE_TYPE != "Voice2Pose":
+        raise ValueError(pre + "ENABLE is a Voice2Pose key (the audio of a train step is augmented before the mel front end), got "
+                         "PIPELINE_TYPE %r" % (cfg.PIPELINE_TYPE,))
+    if not 0 <= seed < 1 << 64:
+        raise ValueError(pre + "SEED must lie in [0, 2^64), got %r" % (seed,))
+    if not 0 <= gain <= 40:
+        raise ValueError(pre + "GAIN_DB must lie in [0, 40], got %r" % (gain,))
+    if snr is not None and not -20 <= snr[0] <= snr[1] <= 80:
+        raise ValueError(pre + "NOISE_SNR_DB [lo, hi] needs -20 <= lo <= hi <= 80, got %r" % (snr,))
+    if not 0 <= prob <= 1:
+        raise ValueError(pre + "NOISE_PROB must lie in [0, 1], got %r" % (prob,))
+    if not 0 <= shift <= 500:
+        raise ValueError(pre + "SHIFT_MS must lie in [0, 500], got %r" % (shift,))
+    for key, (n, w, widest) in masks.items():
+        if not 0 <= n <= 4 or not 0 <= w <= widest:
+            raise ValueError(pre + key + " [n, w] needs n from 0 to 4 and w from 0 to %d, got %r" % (widest, [n, w]))
+    sr = cfg.DATASET.AUDIO_SR
+    if not _is_int(sr) or not 1 <= sr <= 1 << 20:
+        raise ValueError(pre + "SHIFT_MS needs DATASET.AUDIO_SR as an integer from 1 to 2^20, got %r" % (sr,))
+    samples = int(math.floor(float(shift) * sr / 1000.0))
+    noisy = snr is not None and prob > 0
+    if not (gain > 0 or noisy or samples > 0 or pol or any(n > 0 and w > 0 for n, w, _ in masks.values())):
+        raise ValueError(pre + "ENABLE is set while every augmentation sits at its neutral value (GAIN_DB 0, no noise, a shift of 0 samples, "
+                         "no POLARITY, no mel masks): set one, or leave ENABLE off")
+    return {'seed': int(seed), 'gain_db': float(gain), 'snr': None if snr is None else (float(snr[0]), float(snr[1])), 'noise_prob': float(prob),
+            'shift_ms': float(shift), 'shift': samples, 'polarity': pol, 'freq_masks': masks["MEL_FREQ_MASKS"][:2],
+            'time_masks': masks["MEL_TIME_MASKS"][:2]}
 
 
 def check_long_demo(cfg):

@@ -18,7 +18,7 @@ import torch
 from torch import nn
 
 from ... import dp, ops
-from ...config import check_clip_metrics, check_reg_loss
+from ...config import check_augment, check_clip_metrics, check_reg_loss
 from ...mel import MelSpectrogram
 from ...optim import FlatAdam
 from ..datasets.gesture_dataset import PoseTransforms
@@ -33,6 +33,9 @@ class Voice2PoseModel(nn.Module):
         # LAMBDA_VEL / REG_MIN_CONFIDENCE / REG_PART_WEIGHTS, validated; None = all at their defaults: the plain L1 mean (ops.L1LossFn)
         self.reg_opts = check_reg_loss(cfg)
         self._chan_w = {}  # device -> per-channel part weights (2 * 121 floats, x then y), built once
+        # TRAIN.AUGMENT, validated; None = off: no Augmenter exists and the forward pass is the one it was
+        self.aug_opts = check_augment(cfg)
+        self._augmenters = {}  # device -> augment.Augmenter (tables and workspaces), built by the first training forward pass
         self.mel_transfm = MelSpectrogram(win_length=400, hop_length=160, n_fft=512, f_min=55, f_max=7500.0, n_mels=80)
         self.netG = get_model(cfg.VOICE2POSE.GENERATOR.NAME)(cfg)
         code = cfg.VOICE2POSE.GENERATOR.CLIP_CODE
@@ -94,6 +97,13 @@ class Voice2PoseModel(nn.Module):
             self._chan_w[key] = torch.tensor(per_kp * 2, dtype=torch.float32, device=dev)
         return self._chan_w[key]
 
+    def _augmenter(self, dev):
+        key = str(dev)
+        if key not in self._augmenters:
+            from ...augment import Augmenter
+            self._augmenters[key] = Augmenter(self.aug_opts, dev)
+        return self._augmenters[key]
+
     def _eval_code(self, batch, n, dev, poses_gt, dataset, speaker, interpolation_coeff, return_loss):
         """Code selection outside training (voice2pose.py:95-120)."""
         code = self.cfg.VOICE2POSE.GENERATOR.CLIP_CODE
@@ -142,7 +152,16 @@ class Voice2PoseModel(nn.Module):
         else:
             condition_code = None
 
-        mel = self.mel_transfm(audio)
+        if self.training and self.aug_opts is not None:  # TRAIN.AUGMENT: the audio before the mel front end, the mel masks behind it
+            if 'aug_step' not in batch:
+                raise KeyError("TRAIN.AUGMENT.ENABLE is set but the batch has no 'aug_step' (an int64 tensor of shape (1,) with the global "
+                               "step; Voice2Pose.train_step adds it): the augmentation depends on (seed, step, clip)")
+            aug, aug_step = self._augmenter(dev), batch['aug_step'].to(dev, non_blocking=True)
+            aug_clips = clip_indices.long().reshape(-1)
+            audio = aug.audio(audio.float(), aug_clips, aug_step)
+            mel = aug.mel_masks(self.mel_transfm(audio), aug_clips, aug_step)
+        else:
+            mel = self.mel_transfm(audio)
         poses_pred = self.netG(mel, num_frames, condition_code)
         results = {'poses_pred_batch': poses_pred, 'condition_code': condition_code}
         if not return_loss:
@@ -349,6 +368,8 @@ class Voice2Pose(Trainer):
         # SYS.HIP_GRAPH: replay the captured step (forward, metrics, backward, gradient exchange, Adam): the host copies the batch into the graph's
         # static inputs and launches ONE graph instead of ~270 kernels -- on one GPU and under data parallelism alike (graph.GraphedStep captures the
         # RCCL all-reduces with the step, or replays two graphs around an eager exchange; steps that save results run eagerly: they need the final poses)
+        if self.model.aug_opts is not None:  # TRAIN.AUGMENT: the step is an input of the batch, so a replayed graph follows it
+            batch = dict(batch, aug_step=torch.tensor([global_step], dtype=torch.int64))
         losses, results = self.graphed_or_eager_step(batch, eager_ok=not save_step, want_final=bool(save_step))
         self.write_histograms(global_step)  # (SYS.HISTOGRAM_INTERVAL: after the step, outside the captured graph)
         self.last_losses = losses
