@@ -753,6 +753,31 @@ int sdt_clip_gather_audio(const float* audio, int64_t n_audio, const int64_t* a0
                           float* out, int64_t out_elems, int32_t* lengths, void* stream);
 
 /*
+ * Repair of short keypoint dropouts and spikes, an opt-in stage in front of sdt_clip_frame_flags (DESIGN.md section 26 is the contract).
+ * Out of place: src (n_frames, 3, 137) and present are read, src_r (same shape and element type, another buffer) and present_r are
+ * written.  Supported sizes: 1 <= n_frames <= 2^30 (as sdt_clip_workspace_bytes), 0 <= half <= 3, 1 <= max_gap <= 64, 1 <= num_frames
+ * <= 2^24; outside them the size query is negative and the entry points return SDT_ERR_UNSUPPORTED before any launch.  Every float64
+ * operation is rounded on its own, no atomics: the same bits on every call.  All 137 keypoints take part.
+ *   valid: valid0[f, k] = present[f] and x, y finite and not (x <= 3 and y <= 3), compared in the element type.  With half >= 1 a valid0
+ *     point is a spike iff, per coordinate over the m >= 3 valid0 points of frames f-half..f+half of its track (clipped to the video),
+ *     |v - med| > kappa * (1.4826 * mad) + floor_px in x or in y, med = 0.5 * (s[(m-1)/2] + s[m/2]) of the ascending values, mad the
+ *     same median of |s - med|, in float64.  valid = valid0 and not spike; valid and spike are (n_frames, 137) uint8.
+ *   fill: an invalid point with valid frames a < f < b nearest on its track and b - a - 1 <= max_gap becomes
+ *     xa + (xb - xa) * ((f - a) / (b - a)) in float64, rounded once to the element type (x and y), confidence 0, filled[f, k] = 1;
+ *     every other element is copied.  repaired_per_frame[f] = filled keypoints of f among 0, 2..7, 15, 16, 25..136;
+ *     present_r[f] = present[f] or that count is 121.
+ *   clip_counts: repaired_per_clip[c] = sum of repaired_per_frame over [starts[c], starts[c] + num_frames), through an int64 prefix sum
+ *     in workspace (sdt_clip_repair_workspace_bytes(n_frames) bytes, written before it is read).
+ */
+int64_t sdt_clip_repair_workspace_bytes(int64_t n_frames);
+int sdt_clip_repair_valid(int elem_bytes, const void* src, const void* present, int64_t n_frames, int half, double kappa, double floor_px,
+                          uint8_t* valid, uint8_t* spike, void* stream);
+int sdt_clip_repair_fill(int elem_bytes, const void* src, const void* present, const uint8_t* valid, int64_t n_frames, int max_gap, void* src_r,
+                         uint8_t* present_r, uint8_t* filled, int32_t* repaired_per_frame, void* stream);
+int sdt_clip_repair_clip_counts(const int32_t* repaired_per_frame, int64_t n_frames, const int32_t* starts, int64_t n_clips, int num_frames,
+                                void* workspace, int64_t workspace_bytes, int32_t* repaired_per_clip, void* stream);
+
+/*
  * Optimiser-side safeguards of the flat-buffer Adam (no counterpart in the reference): gradient-norm clipping as
  * torch.nn.utils.clip_grad_norm_(norm_type=2, error_if_nonfinite=False), a step that a non-finite gradient cannot poison, and an
  * exponential moving average of the parameters.  No atomics, no host read-back: hipGraph-capturable like the rest.

@@ -13,6 +13,7 @@ bit.  The models exist for the tests; ``build_clips`` has no CPU fallback.
 
     python -m speechdrivestemplates_amd.clip_builder --root DIR --speaker NAME [--start-frame 80] [--frames 64]
                                                      [--shoulder-chunks 1] [--no-write]
+                                                     [--repair-max-gap G] [--despike H KAPPA [FLOOR_PX]]   (section 26, off by default)
 """
 import argparse
 import ctypes as C
@@ -206,6 +207,121 @@ def split_labels(n, val_label='dev'):
     return ['train'] * n_train + ['idle'] * n_idle + [val_label] * (n - n_train - n_idle)
 
 
+# ---------------------------------------------------------------------------------------- repair of dropouts and spikes (section 26)
+
+MAX_GAP, MAX_HALF = 64, 3  # the library's limits (sdt_clip_repair_fill, sdt_clip_repair_valid)
+
+
+def repair_params(max_gap, despike=None):
+    """-> (max_gap, None or (h, kappa, floor_px)) as ints / floats; a ValueError names what is out of range"""
+    if int(max_gap) != max_gap or not 1 <= int(max_gap) <= MAX_GAP:
+        raise ValueError('repair_max_gap must be an integer in 1..%d, not %r' % (MAX_GAP, max_gap))
+    if despike is None:
+        return int(max_gap), None
+    d = tuple(despike)
+    if len(d) == 2:
+        d = d + (0.0,)
+    if len(d) != 3:
+        raise ValueError('despike is (h, kappa) or (h, kappa, floor_px), not %r' % (despike,))
+    h, kappa, floor_px = d
+    if int(h) != h or not 1 <= int(h) <= MAX_HALF:
+        raise ValueError('despike h must be an integer in 1..%d, not %r' % (MAX_HALF, h))
+    if not (np.isfinite(kappa) and kappa > 0) or not (np.isfinite(floor_px) and floor_px >= 0):
+        raise ValueError('despike kappa must be positive and floor_px not negative, both finite, not %r, %r' % (kappa, floor_px))
+    return int(max_gap), (int(h), float(kappa), float(floor_px))
+
+
+def model_valid(src, present):
+    """src (n, 3, 137), present (n,) -> (n, 137) bool: the 2_2 rule per point (x <= 3 and y <= 3 is invalid, compared in src's dtype)
+    on frames with a file; a non-finite coordinate is invalid"""
+    x, y = src[:, 0, :], src[:, 1, :]
+    with np.errstate(invalid='ignore'):
+        low = (x <= 3) & (y <= 3)
+    return np.asarray(present, bool)[:, None] & np.isfinite(x) & np.isfinite(y) & ~low
+
+
+def _window_median(s, m):
+    """s (w, ...) ascending along axis 0 with +inf behind the m values -> 0.5 * (s[(m-1)//2] + s[m//2])"""
+    lo = np.take_along_axis(s, ((m - 1) // 2)[None], axis=0)[0]
+    hi = np.take_along_axis(s, (m // 2)[None], axis=0)[0]
+    return 0.5 * (lo + hi)
+
+
+def model_despike(src, valid, h, kappa, floor_px):
+    """-> spike (n, 137) bool.  A valid point is tested against the m >= 3 valid points of frames f-h..f+h of its track (centre
+    included, clipped to the video), per coordinate in float64: |v - med| > kappa * (1.4826 * mad) + floor_px in x or in y.  Every
+    verdict comes from ``valid`` as given, none from another verdict."""
+    n = src.shape[0]
+    ok = np.zeros((2 * h + 1, n, KP), bool)
+    for i, d in enumerate(range(-h, h + 1)):
+        lo, hi = max(0, -d), min(n, n - d)  # frames f with 0 <= f + d < n
+        if lo < hi:
+            ok[i, lo:hi] = valid[lo + d:hi + d]
+    m = ok.sum(axis=0)
+    m_safe = np.maximum(m, 1)
+    spike = np.zeros((n, KP), bool)
+    with np.errstate(invalid='ignore', over='ignore'):
+        for c in (0, 1):
+            v = src[:, c, :].astype(np.float64)
+            win = np.full((2 * h + 1, n, KP), np.inf)
+            for i, d in enumerate(range(-h, h + 1)):
+                lo, hi = max(0, -d), min(n, n - d)
+                if lo < hi:
+                    win[i, lo:hi] = np.where(ok[i, lo:hi], v[lo + d:hi + d], np.inf)
+            s = np.sort(win, axis=0)
+            med = _window_median(s, m_safe)
+            dev = np.sort(np.where(np.arange(2 * h + 1)[:, None, None] < m[None], np.abs(s - med[None]), np.inf), axis=0)
+            mad = _window_median(dev, m_safe)
+            bar = kappa * (1.4826 * mad) + floor_px
+            spike |= valid & (m >= 3) & (np.abs(v - med) > bar)
+    return spike
+
+
+def model_repair(src, present, max_gap, despike=None):
+    """-> dict(src_r, present_r (n,) bool, valid, spike, filled (n, 137) bool, repaired_per_frame (n,) int32).  An invalid point with
+    valid frames a < f < b nearest on its track and b - a - 1 <= max_gap becomes xa + (xb - xa) * ((f - a) / (b - a)) in float64,
+    every operation rounded on its own, rounded once to src's dtype, with confidence 0; nothing else changes"""
+    max_gap, despike = repair_params(max_gap, despike)
+    n = src.shape[0]
+    present = np.asarray(present, bool)
+    valid0 = model_valid(src, present)
+    spike = model_despike(src, valid0, *despike) if despike is not None else np.zeros((n, KP), bool)
+    valid = valid0 & ~spike
+    idx = np.arange(n, dtype=np.int64)[:, None]
+    a = np.maximum.accumulate(np.where(valid, idx, -1), axis=0)            # the last valid frame at or before f
+    b = np.minimum.accumulate(np.where(valid, idx, n)[::-1], axis=0)[::-1]  # the first valid frame at or after f
+    filled = ~valid & (a >= 0) & (b < n) & (b - a - 1 <= max_gap)
+    a_s, b_s = np.where(filled, a, 0), np.where(filled, b, 0)
+    t = (idx - a_s).astype(np.float64) / np.where(filled, b_s - a_s, 1).astype(np.float64)
+    out = src.copy()
+    for c in (0, 1):
+        v = src[:, c, :].astype(np.float64)
+        va, vb = np.take_along_axis(v, a_s, axis=0), np.take_along_axis(v, b_s, axis=0)
+        with np.errstate(invalid='ignore', over='ignore'):
+            fill = (va + (vb - va) * t).astype(src.dtype)
+        out[:, c, :] = np.where(filled, fill, src[:, c, :])
+    out[:, 2, :] = np.where(filled, src.dtype.type(0), src[:, 2, :])
+    per_frame = filled[:, KEEP_121].sum(axis=1).astype(np.int32)
+    return {'src_r': out, 'present_r': present | (per_frame == len(KEEP_121)), 'valid': valid, 'spike': spike, 'filled': filled,
+            'repaired_per_frame': per_frame}
+
+
+def model_repaired_per_clip(repaired_per_frame, starts, num_frames):
+    """the filled kept keypoints of each window, through an integer prefix sum"""
+    pre = np.concatenate([[0], np.cumsum(np.asarray(repaired_per_frame, np.int64))])
+    return np.array([pre[s + num_frames] - pre[s] for s in starts], np.int32)
+
+
+def model_repair_summary(present, keep0, keep_r, rep, starts0, starts_r, per_clip, num_frames):
+    """the ``repair`` entry of a video's summary from the stage's records (counts on the host, exact integers)"""
+    return {'points_filled': int(rep['filled'].sum()), 'spikes': int(rep['spike'].sum()),
+            'spikes_unfilled': int((rep['spike'].astype(bool) & ~rep['filled'].astype(bool)).sum()),
+            'frames_recovered': int((np.asarray(keep_r, bool) & ~np.asarray(keep0, bool)).sum()),
+            'missing_recovered': int((np.asarray(rep['present_r'], bool) & ~np.asarray(present, bool)).sum()),
+            'clips_without_repair': len(starts0), 'clips_with_repair': len(starts_r),
+            'max_repaired_share': float(max(per_clip) / (num_frames * len(KEEP_121))) if len(per_clip) else 0.0}
+
+
 # ----------------------------------------------------------------------------------------------------------------------- host I/O
 
 def _read_frames(video, dtype, pool):
@@ -344,6 +460,59 @@ def device_frame_stages(src, present, start_frame, num_frames, shoulder_chunks, 
     return o
 
 
+def _check_size(status):
+    """as ``_lib.check``; the library's "unsupported size" status becomes a ValueError"""
+    from . import _lib
+    if status == -3:  # SDT_ERR_UNSUPPORTED
+        raise ValueError('libsdt_hip: %s' % _lib.load().sdt_last_error().decode())
+    _lib.check(status)
+
+
+def device_repair(src, present, max_gap, despike=None, timer=None):
+    """the repair stage of one video (section 26).  src (n, 3, 137) and present (n,) uint8 on the device, neither written ->
+    dict(src_r, present_r (n,) uint8, valid, spike, filled (n, 137) uint8, repaired_per_frame (n,) int32).  The sizes are the
+    library's to refuse: an unsupported max_gap, h or n is a ValueError"""
+    import torch
+    from . import _lib
+    lib = _lib.load()
+    dev, n = src.device, src.shape[0]
+    h, kappa, floor_px = (0, 1.0, 0.0) if despike is None else (despike if len(despike) == 3 else tuple(despike) + (0.0,))
+    if despike is not None and (not (np.isfinite(kappa) and kappa > 0) or not (np.isfinite(floor_px) and floor_px >= 0)):
+        raise ValueError('despike kappa must be positive and floor_px not negative, both finite, not %r, %r' % (kappa, floor_px))
+    if lib.sdt_clip_repair_workspace_bytes(n) < 0:
+        raise ValueError('unsupported frame count %d' % n)
+    raw = torch.cuda.current_stream(dev).cuda_stream
+    esize = src.element_size()
+    o = {'src_r': torch.empty_like(src), 'present_r': torch.empty(n, dtype=torch.uint8, device=dev),
+         'valid': torch.empty((n, KP), dtype=torch.uint8, device=dev), 'spike': torch.empty((n, KP), dtype=torch.uint8, device=dev),
+         'filled': torch.empty((n, KP), dtype=torch.uint8, device=dev), 'repaired_per_frame': torch.empty(n, dtype=torch.int32, device=dev)}
+
+    def launch():
+        _check_size(lib.sdt_clip_repair_valid(esize, _p(src), _p(present), n, int(h), float(kappa), float(floor_px), _p(o['valid']),
+                                              _p(o['spike']), raw))
+        _check_size(lib.sdt_clip_repair_fill(esize, _p(src), _p(present), _p(o['valid']), n, int(max_gap), _p(o['src_r']), _p(o['present_r']),
+                                             _p(o['filled']), _p(o['repaired_per_frame']), raw))
+    if timer is not None:
+        timer.run('repair', launch)
+    else:
+        launch()
+    return o
+
+
+def device_repaired_per_clip(repaired_per_frame, starts, n_clips, num_frames):
+    """-> (n_clips,) int32: the filled kept keypoints of each window"""
+    import torch
+    from . import _lib
+    lib = _lib.load()
+    dev, n = repaired_per_frame.device, repaired_per_frame.shape[0]
+    out = torch.empty(n_clips, dtype=torch.int32, device=dev)
+    if n_clips:
+        ws = torch.empty(lib.sdt_clip_repair_workspace_bytes(n), dtype=torch.uint8, device=dev)
+        _check_size(lib.sdt_clip_repair_clip_counts(_p(repaired_per_frame), n, _p(starts), n_clips, num_frames, _p(ws), ws.numel(), _p(out),
+                                                    torch.cuda.current_stream(dev).cuda_stream))
+    return out
+
+
 def device_gather_poses(src, starts, n_clips, num_frames, scalar, scale_conf):
     """-> (n_clips, num_frames, 3, 137) in src's dtype"""
     import torch
@@ -414,10 +583,13 @@ def device_gather_audio(audio, a0, a1):
     return out, lengths
 
 
-def build_clips(root_dir, speaker, start_frame=80, num_frames=64, shoulder_chunks=1, scale_confidence=None, write=True, device='cuda'):
+def build_clips(root_dir, speaker, start_frame=80, num_frames=64, shoulder_chunks=1, scale_confidence=None, write=True, device='cuda',
+                repair_max_gap=0, despike=None):
     """-> {'videos': {name: summary}, 'table' (processed_137 order), 'timing'} and, with write=False, 'poses' (n_clips, num_frames, 3, 137),
     'audio' (n_clips, L_max), 'audio_lengths' (n_clips,) on the device in per-video, ascending-start order, with 'order' giving
-    each table row's position in them"""
+    each table row's position in them.  ``repair_max_gap`` G >= 1 (with ``despike`` = (h, kappa, floor_px) or None) runs the repair
+    stage of section 26 in front of the frame flags: each video's summary gains 'repair' and, with write=False, the result
+    'repaired_per_clip' (n_clips,) int32; with 0 nothing new is launched"""
     import torch
     from . import _lib
     dev = torch.device(device)
@@ -426,6 +598,11 @@ def build_clips(root_dir, speaker, start_frame=80, num_frames=64, shoulder_chunk
     _lib.load()
     if int(shoulder_chunks) < 1 or int(num_frames) < 1 or int(start_frame) < 0:
         raise ValueError('shoulder_chunks and num_frames must be at least 1, start_frame at least 0')
+    repair = bool(repair_max_gap)
+    if despike is not None and not repair:
+        raise ValueError('despike needs repair_max_gap >= 1: a marked spike is repaired by the gap filling')
+    if repair:
+        repair_max_gap, despike = repair_params(repair_max_gap, despike)
     plan = plan_clips(root_dir, speaker)
     first = next((p for v in plan for p in v['frames'].values()), None)
     if first is None:
@@ -441,7 +618,7 @@ def build_clips(root_dir, speaker, start_frame=80, num_frames=64, shoulder_chunk
         os.makedirs(os.path.join(base, 'tmp', 'intermediate_csv'), exist_ok=True)
     st = torch.cuda.current_stream(dev)
     pool = ThreadPoolExecutor(max_workers=MAX_READ_THREADS)
-    summary, tables, all_poses, all_audio, all_len = {}, [], [], [], []
+    summary, tables, all_poses, all_audio, all_len, all_rep = {}, [], [], [], [], []
     t_all = time.perf_counter()
     try:
         for video in plan:
@@ -454,11 +631,17 @@ def build_clips(root_dir, speaker, start_frame=80, num_frames=64, shoulder_chunk
             t_read = time.perf_counter() - t0
             timer = _Timer(st)
             src = src_host.to(dev, non_blocking=True)
-            o = device_frame_stages(src, torch.from_numpy(present).to(dev), start_frame, num_frames, shoulder_chunks, timer)
+            present_dev = torch.from_numpy(present).to(dev)
+            if repair:
+                o0 = device_frame_stages(src, present_dev, start_frame, num_frames, shoulder_chunks)  # what the unrepaired tracks give
+                rep = device_repair(src, present_dev, repair_max_gap, despike, timer)
+                src, present_dev = rep['src_r'], rep['present_r']
+            o = device_frame_stages(src, present_dev, start_frame, num_frames, shoulder_chunks, timer)
             n_clips = int(o['n_clips'].item())  # (synchronises)
             bad = o['bad'].cpu().numpy()
             if bad.any():
-                raise ValueError('%s: non-finite keypoint coordinates' % video['frames'][int(np.flatnonzero(bad)[0])])
+                f_bad = int(np.flatnonzero(bad)[0])
+                raise ValueError('%s: non-finite keypoint coordinates' % video['frames'].get(f_bad, '%s frame %d' % (video['dir'], f_bad)))
             n_kept = int(o['prefix'][n].item())
             if n_kept == 0:
                 raise ValueError('%s: no kept frame (every frame is an outlier)' % video['dir'])
@@ -479,6 +662,17 @@ def build_clips(root_dir, speaker, start_frame=80, num_frames=64, shoulder_chunk
             timer.run('gather_audio', lambda: holder.__setitem__('clips', device_gather_audio(holder['audio'], [a for a, _ in offs], [b for _, b in offs])))
             torch.cuda.synchronize(dev)
             poses, (audio, lengths) = holder['poses'], holder['clips']
+            n_present = int(present.sum())
+            rep_summary = None
+            if repair:
+                per_clip = device_repaired_per_clip(rep['repaired_per_frame'], o['starts'], n_clips, num_frames)
+                host = {k: rep[k].cpu().numpy() for k in ('filled', 'spike', 'present_r')}
+                n0 = int(o0['n_clips'].item())
+                rep_summary = model_repair_summary(present, o0['keep'].cpu().numpy(), o['keep'].cpu().numpy(), host,
+                                                   range(n0), starts, per_clip.cpu().numpy(), num_frames)
+                n_present = int(host['present_r'].sum())  # (the files and the frames the stage gave back)
+                if not write:
+                    all_rep.append(per_clip)
             table = video_table(speaker, name, starts, num_frames)
             tables.append(table)
             t_write = 0.0
@@ -498,12 +692,13 @@ def build_clips(root_dir, speaker, start_frame=80, num_frames=64, shoulder_chunk
                 all_audio.append(audio)
                 all_len.append(lengths)
             labels = split_labels(n_clips)
-            n_present = int(present.sum())
-            summary[name] = {'frames': n, 'missing': n - n_present, 'kept': n_kept, 'dropped': n - n_kept, 'outliers': n_present - n_kept,
+            summary[name] = {'frames': n, 'missing': n - int(present.sum()), 'kept': n_kept, 'dropped': n - n_kept, 'outliers': n_present - n_kept,
                              'shoulder_dropped': n_kept - (n_kept // shoulder_chunks) * shoulder_chunks, 'scalar': scalar,
                              'scale_confidence': scale_conf, 'sample_rate': sr_in, 'audio_samples': int(holder['audio'].numel()),
                              'clips': {lab: labels.count(lab) for lab in ('train', 'idle', 'dev')},
                              'timing': {'kernel_ms': timer.totals(), 'read_s': t_read, 'write_s': t_write}}
+            if repair:
+                summary[name]['repair'] = rep_summary
     finally:
         pool.shutdown()
     import pandas as pd
@@ -519,8 +714,26 @@ def build_clips(root_dir, speaker, start_frame=80, num_frames=64, shoulder_chunk
         out['poses'] = torch.cat(all_poses) if all_poses else torch.empty((0, num_frames, 3, KP), dtype=dtype, device=dev)
         out['audio'] = torch.cat([torch.nn.functional.pad(a, (0, l_max - a.shape[1])) for a in all_audio])
         out['audio_lengths'] = torch.cat(all_len)
+        if repair:
+            out['repaired_per_clip'] = torch.cat(all_rep)
     assert isinstance(out['table'], pd.DataFrame)
     return out
+
+
+def add_repair_options(ap):
+    ap.add_argument('--repair-max-gap', type=int, default=0, metavar='G',
+                    help='fill gaps of at most G (1..64) frames in a keypoint track by interpolation, confidence 0 (0: off)')
+    ap.add_argument('--despike', nargs='+', type=float, default=None, metavar=('H', 'KAPPA'),
+                    help='H KAPPA [FLOOR_PX]: mark a point more than KAPPA * 1.4826 * MAD + FLOOR_PX from the median of frames -H..H (H in 1..3) '
+                         'of its track and fill it like a gap (needs --repair-max-gap)')
+
+
+def despike_option(ap, values):
+    if values is None:
+        return None
+    if len(values) not in (2, 3) or values[0] != int(values[0]):
+        ap.error('--despike takes H KAPPA [FLOOR_PX] with an integer H')
+    return (int(values[0]),) + tuple(values[1:]) + ((0.0,) if len(values) == 2 else ())
 
 
 def main(argv=None):
@@ -532,14 +745,21 @@ def main(argv=None):
     ap.add_argument('--frames', type=int, default=64, help='frames per clip (DATASET.NUM_FRAMES)')
     ap.add_argument('--shoulder-chunks', type=int, default=1, help="chunks of the shoulder-distance mean (2_3's -np)")
     ap.add_argument('--no-write', action='store_true', help='build on the device and print the summary only')
+    add_repair_options(ap)
     a = ap.parse_args(argv)
-    res = build_clips(a.root, a.speaker, start_frame=a.start_frame, num_frames=a.frames, shoulder_chunks=a.shoulder_chunks, write=not a.no_write)
+    res = build_clips(a.root, a.speaker, start_frame=a.start_frame, num_frames=a.frames, shoulder_chunks=a.shoulder_chunks, write=not a.no_write,
+                      repair_max_gap=a.repair_max_gap, despike=despike_option(ap, a.despike))
     for name, s in res['videos'].items():
         k = s['timing']
+        r = s.get('repair')
+        fixed = '' if r is None else (', repair filled %d points, %d spikes (%d not filled), %d frames recovered (%d without a file), clips %d -> %d, '
+                                      'largest repaired share of a clip %.4f'
+                                      % (r['points_filled'], r['spikes'], r['spikes_unfilled'], r['frames_recovered'], r['missing_recovered'],
+                                         r['clips_without_repair'], r['clips_with_repair'], r['max_repaired_share']))
         print('video %s: %d frames, %d kept, %d dropped (%d missing), %d shoulder frames dropped by chunking, scalar %.9g, clips %d train / '
-              '%d idle / %d dev (%.2f s reading, kernels %.3f ms, %.2f s writing)'
+              '%d idle / %d dev (%.2f s reading, kernels %.3f ms, %.2f s writing)%s'
               % (name, s['frames'], s['kept'], s['dropped'], s['missing'], s['shoulder_dropped'], s['scalar'], s['clips']['train'],
-                 s['clips']['idle'], s['clips']['dev'], k['read_s'], sum(k['kernel_ms'].values()), k['write_s']))
+                 s['clips']['idle'], s['clips']['dev'], k['read_s'], sum(k['kernel_ms'].values()), k['write_s'], fixed))
     print('speaker %s: %d clips in %.2f s%s' % (a.speaker, len(res['table']), res['timing']['total_s'],
                                                 '' if a.no_write else ' -> ' + res['files']['processed_137.csv']))
     return 0

@@ -10,8 +10,10 @@
 //   pcm              integer / float PCM -> float32, channels averaged
 //   resample         polyphase FIR with float64 taps, float64 accumulation in ascending tap order, one rounding to float32
 //   audio gather     per-clip slices with a length table
+//   repair (opt-in)  in front of the frame flags: per-point validity and spike marks, gap filling by interpolation into a second
+//                    buffer, the filled points per frame and per clip (integers)
 // Every floating-point operation is rounded on its own (contraction is off for the whole file) and no floating-point value is
-// accumulated with atomics, so every output is a fixed function of the inputs.  Contract and numbers: DESIGN.md section 16.
+// accumulated with atomics, so every output is a fixed function of the inputs.  Contract and numbers: DESIGN.md sections 16 and 26.
 #include "common.h"
 
 #pragma clang fp contract(off)
@@ -259,6 +261,193 @@ __global__ void __launch_bounds__(kThreads) clip_gather_audio_kernel(const float
     if (i < l_max) out[(int64_t)c * l_max + i] = i < len ? audio[b + i] : 0.f;
 }
 
+// ------------------------------------------------------------------------------------------------------------------------- repair
+// Opt-in stage in front of the frame flags: short gaps of a keypoint's track are filled by interpolation between
+// the nearest valid frames, isolated jumps are marked first and filled the same way.  Out of place: src is read, src_r is written.
+
+constexpr int kRepairMaxGap = 64, kRepairMaxHalf = 3, kRepairWin = 2 * kRepairMaxHalf + 1;
+
+// the 2_2 rule per point, on a frame that has a file; a non-finite coordinate is invalid
+template <typename T>
+__device__ __forceinline__ bool point_valid(const T* __restrict__ src, const uint8_t* __restrict__ present, int64_t f, int k, T* x_out, T* y_out) {
+    const T x = src[f * kFrameElems + k], y = src[f * kFrameElems + kKp + k];
+    *x_out = x;
+    *y_out = y;
+    return present[f] != 0 && isfinite(x) && isfinite(y) && !(x <= T(3) && y <= T(3));
+}
+
+// ascending; the unused slots hold +inf and end up behind the m values
+__device__ __forceinline__ void sort_win(double (&s)[kRepairWin]) {
+#pragma unroll
+    for (int i = 0; i < kRepairWin - 1; ++i) {
+#pragma unroll
+        for (int j = 0; j < kRepairWin - 1 - i; ++j) {
+            const double a = s[j], b = s[j + 1];
+            const bool swap = a > b;
+            s[j] = swap ? b : a;
+            s[j + 1] = swap ? a : b;
+        }
+    }
+}
+
+__device__ __forceinline__ double median_win(const double (&s)[kRepairWin], int m) {
+    const int lo = (m - 1) / 2, hi = m / 2;
+    double a = 0.0, b = 0.0;
+#pragma unroll
+    for (int i = 0; i < kRepairWin; ++i) {
+        if (i == lo) a = s[i];
+        if (i == hi) b = s[i];
+    }
+    return 0.5 * (a + b);
+}
+
+// |v - med| > kappa * (1.4826 * mad) + floor_px over the m values of s (m >= 3, the other slots +inf)
+__device__ __forceinline__ bool spike_coord(double (&s)[kRepairWin], int m, double v, double kappa, double floor_px) {
+    sort_win(s);
+    const double med = median_win(s, m);
+    double d[kRepairWin];
+#pragma unroll
+    for (int i = 0; i < kRepairWin; ++i) d[i] = i < m ? fabs(s[i] - med) : (double)INFINITY;
+    sort_win(d);
+    const double mad = median_win(d, m);
+    const double bar = kappa * (1.4826 * mad) + floor_px;
+    return fabs(v - med) > bar;
+}
+
+// one thread per (frame, keypoint): valid = the point's own test, minus the spikes; every verdict reads src alone
+template <typename T>
+__global__ void __launch_bounds__(kThreads) clip_repair_valid_kernel(const T* __restrict__ src, const uint8_t* __restrict__ present, int64_t n,
+                                                                     int half, double kappa, double floor_px, uint8_t* __restrict__ valid,
+                                                                     uint8_t* __restrict__ spike) {
+    const int64_t idx = (int64_t)blockIdx.x * kThreads + threadIdx.x;
+    if (idx >= n * kKp) return;
+    const int64_t f = idx / kKp;
+    const int k = (int)(idx % kKp);
+    T x, y;
+    const bool ok = point_valid(src, present, f, k, &x, &y);
+    bool sp = false;
+    if (half > 0 && ok) {
+        double xs[kRepairWin], ys[kRepairWin];
+        int m = 0;
+#pragma unroll
+        for (int d = -kRepairMaxHalf; d <= kRepairMaxHalf; ++d) {
+            const int64_t g = f + d;
+            T gx = T(0), gy = T(0);
+            const bool in = d >= -half && d <= half && g >= 0 && g < n && point_valid(src, present, g, k, &gx, &gy);
+            xs[d + kRepairMaxHalf] = in ? (double)gx : (double)INFINITY;
+            ys[d + kRepairMaxHalf] = in ? (double)gy : (double)INFINITY;
+            m += in ? 1 : 0;
+        }
+        if (m >= 3) {
+            const bool sx = spike_coord(xs, m, (double)x, kappa, floor_px), sy = spike_coord(ys, m, (double)y, kappa, floor_px);
+            sp = sx || sy;
+        }
+    }
+    valid[idx] = (ok && !sp) ? 1 : 0;
+    spike[idx] = sp ? 1 : 0;
+}
+
+// one wave per group of frames, lanes over the keypoints.  An invalid point looks back and forth along its track for the nearest
+// valid frames a < f < b (at most max_gap + 1 steps in all: b - a - 1 <= max_gap) and is filled with xa + (xb - xa) * ((f - a) / (b - a))
+// in float64, rounded once to T, confidence 0; the filled kept keypoints of a frame are counted with ballots.
+template <typename T>
+__global__ void __launch_bounds__(kThreads) clip_repair_fill_kernel(const T* __restrict__ src, const uint8_t* __restrict__ present,
+                                                                    const uint8_t* __restrict__ valid, int64_t n, int max_gap,
+                                                                    T* __restrict__ src_r, uint8_t* __restrict__ present_r,
+                                                                    uint8_t* __restrict__ filled, int32_t* __restrict__ per_frame) {
+    const int64_t wave = ((int64_t)blockIdx.x * kThreads + threadIdx.x) / 64;
+    const int lane = threadIdx.x & 63;
+    for (int g = 0; g < kFramesPerWave; ++g) {
+        const int64_t f = wave * kFramesPerWave + g;
+        if (f >= n) break;  // uniform over the wave
+        const T* p = src + f * kFrameElems;
+        T* q = src_r + f * kFrameElems;
+        int count = 0;
+        for (int k0 = 0; k0 < kKp; k0 += 64) {  // (uniform: every lane reaches the ballot)
+            const int k = k0 + lane;
+            bool fill = false;
+            if (k < kKp) {
+                T x = p[k], y = p[kKp + k], c = p[2 * kKp + k];
+                if (valid[f * kKp + k] == 0) {
+                    int64_t a = -1, b = -1;
+                    for (int d = 1; d <= max_gap && f - d >= 0; ++d) {
+                        if (valid[(f - d) * kKp + k] != 0) {
+                            a = f - d;
+                            break;
+                        }
+                    }
+                    if (a >= 0) {
+                        const int reach = max_gap + 1 - (int)(f - a);  // b <= a + max_gap + 1
+                        for (int d = 1; d <= reach && f + d < n; ++d) {
+                            if (valid[(f + d) * kKp + k] != 0) {
+                                b = f + d;
+                                break;
+                            }
+                        }
+                    }
+                    if (b >= 0) {
+                        const T* pa = src + a * kFrameElems;
+                        const T* pb = src + b * kFrameElems;
+                        const double t = (double)(f - a) / (double)(b - a);
+                        const double xa = (double)pa[k], xb = (double)pb[k], ya = (double)pa[kKp + k], yb = (double)pb[kKp + k];
+                        x = (T)(xa + (xb - xa) * t);
+                        y = (T)(ya + (yb - ya) * t);
+                        c = T(0);
+                        fill = true;
+                    }
+                }
+                q[k] = x;
+                q[kKp + k] = y;
+                q[2 * kKp + k] = c;
+                filled[f * kKp + k] = fill ? 1 : 0;
+            }
+            count += __popcll(__ballot(fill && kept121(k)));
+        }
+        if (lane == 0) {
+            per_frame[f] = count;
+            present_r[f] = (present[f] != 0 || count == 121) ? 1 : 0;
+        }
+    }
+}
+
+// one workgroup walks the frames in tiles of kThreads: prefix[f] = repaired kept keypoints before frame f (integers), prefix[n] = all
+__global__ void __launch_bounds__(kThreads) clip_repair_prefix_kernel(const int32_t* __restrict__ per_frame, int64_t n, int64_t* __restrict__ prefix) {
+    __shared__ int wsum[kThreads / 64];
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    int64_t carry = 0;
+    for (int64_t base = 0; base < n; base += kThreads) {
+        const int64_t f = base + threadIdx.x;
+        const int v = f < n ? per_frame[f] : 0;
+        int incl = v;
+#pragma unroll
+        for (int off = 1; off < 64; off <<= 1) {
+            const int t = __shfl_up(incl, off);
+            if (lane >= off) incl += t;
+        }
+        if (lane == 63) wsum[w] = incl;
+        __syncthreads();
+        int woff = 0, tot = 0;
+#pragma unroll
+        for (int i = 0; i < kThreads / 64; ++i) {
+            if (i < w) woff += wsum[i];
+            tot += wsum[i];
+        }
+        if (f < n) prefix[f] = carry + woff + incl - v;
+        carry += tot;
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) prefix[n] = carry;
+}
+
+__global__ void __launch_bounds__(kThreads) clip_repair_clip_counts_kernel(const int64_t* __restrict__ prefix, int64_t n,
+                                                                           const int32_t* __restrict__ starts, int64_t n_clips, int F,
+                                                                           int32_t* __restrict__ out) {
+    const int64_t c = (int64_t)blockIdx.x * kThreads + threadIdx.x;
+    if (c >= n_clips) return;
+    const int64_t s = starts[c];
+    out[c] = (s >= 0 && s + F <= n) ? (int32_t)(prefix[s + F] - prefix[s]) : -1;  // (the pack pass only emits windows inside the video)
+}
+
 struct ResPlan {
     int q_max, span_max, slots, tiles_per_block;
     int64_t lds;
@@ -408,6 +597,67 @@ extern "C" int sdt_clip_gather_audio(const float* audio, int64_t n_audio, const 
     SDT_CHECK_ARG(out_elems >= n_clips * l_max, "output buffer too small");
     hipLaunchKernelGGL(clip_gather_audio_kernel, dim3((unsigned)cdiv64(l_max, kThreads), (unsigned)n_clips), dim3(kThreads), 0, (hipStream_t)stream,
                        audio, n_audio, a0, a1, l_max, out, lengths);
+    SDT_LAUNCH_CHECK();
+    return SDT_OK;
+}
+
+extern "C" int64_t sdt_clip_repair_workspace_bytes(int64_t n_frames) {
+    if (n_frames <= 0 || n_frames > (1 << 30)) return -1;
+    return (n_frames + 1) * (int64_t)sizeof(int64_t);  // the prefix sum of repaired_per_frame
+}
+
+extern "C" int sdt_clip_repair_valid(int elem_bytes, const void* src, const void* present, int64_t n_frames, int half, double kappa,
+                                     double floor_px, uint8_t* valid, uint8_t* spike, void* stream) {
+    SDT_CHECK_SUPPORTED(n_frames > 0 && n_frames <= (1 << 30), "unsupported size: frame count outside [1, 2^30]");
+    SDT_CHECK_SUPPORTED(half >= 0 && half <= kRepairMaxHalf, "unsupported size: despike half window outside [0, 3]");
+    SDT_CHECK_ARG(elem_bytes == 4 || elem_bytes == 8, "elem_bytes must be 4 (float32 keypoints) or 8 (float64 keypoints)");
+    SDT_CHECK_ARG(src != nullptr && present != nullptr && valid != nullptr && spike != nullptr, "null pointer");
+    SDT_CHECK_ARG(half == 0 || (kappa > 0.0 && kappa <= 1.0e300 && floor_px >= 0.0 && floor_px <= 1.0e300), "kappa must be positive, floor_px not negative, both finite");
+    const unsigned grid = (unsigned)cdiv64(n_frames * kKp, kThreads);
+    hipStream_t st = (hipStream_t)stream;
+    if (elem_bytes == 4)
+        hipLaunchKernelGGL((clip_repair_valid_kernel<float>), dim3(grid), dim3(kThreads), 0, st, (const float*)src, (const uint8_t*)present,
+                           n_frames, half, kappa, floor_px, valid, spike);
+    else
+        hipLaunchKernelGGL((clip_repair_valid_kernel<double>), dim3(grid), dim3(kThreads), 0, st, (const double*)src, (const uint8_t*)present,
+                           n_frames, half, kappa, floor_px, valid, spike);
+    SDT_LAUNCH_CHECK();
+    return SDT_OK;
+}
+
+extern "C" int sdt_clip_repair_fill(int elem_bytes, const void* src, const void* present, const uint8_t* valid, int64_t n_frames, int max_gap,
+                                    void* src_r, uint8_t* present_r, uint8_t* filled, int32_t* repaired_per_frame, void* stream) {
+    SDT_CHECK_SUPPORTED(n_frames > 0 && n_frames <= (1 << 30), "unsupported size: frame count outside [1, 2^30]");
+    SDT_CHECK_SUPPORTED(max_gap >= 1 && max_gap <= kRepairMaxGap, "unsupported size: max_gap outside [1, 64]");
+    SDT_CHECK_ARG(elem_bytes == 4 || elem_bytes == 8, "elem_bytes must be 4 (float32 keypoints) or 8 (float64 keypoints)");
+    SDT_CHECK_ARG(src != nullptr && present != nullptr && valid != nullptr && src_r != nullptr && present_r != nullptr && filled != nullptr &&
+                      repaired_per_frame != nullptr,
+                  "null pointer");
+    SDT_CHECK_ARG(src != src_r, "the stage is out of place: src_r must not be src");
+    const unsigned grid = (unsigned)cdiv64(n_frames, (int64_t)kFramesPerWave * (kThreads / 64));
+    hipStream_t st = (hipStream_t)stream;
+    if (elem_bytes == 4)
+        hipLaunchKernelGGL((clip_repair_fill_kernel<float>), dim3(grid), dim3(kThreads), 0, st, (const float*)src, (const uint8_t*)present, valid,
+                           n_frames, max_gap, (float*)src_r, present_r, filled, repaired_per_frame);
+    else
+        hipLaunchKernelGGL((clip_repair_fill_kernel<double>), dim3(grid), dim3(kThreads), 0, st, (const double*)src, (const uint8_t*)present, valid,
+                           n_frames, max_gap, (double*)src_r, present_r, filled, repaired_per_frame);
+    SDT_LAUNCH_CHECK();
+    return SDT_OK;
+}
+
+extern "C" int sdt_clip_repair_clip_counts(const int32_t* repaired_per_frame, int64_t n_frames, const int32_t* starts, int64_t n_clips,
+                                           int num_frames, void* workspace, int64_t workspace_bytes, int32_t* repaired_per_clip, void* stream) {
+    SDT_CHECK_SUPPORTED(n_frames > 0 && n_frames <= (1 << 30), "unsupported size: frame count outside [1, 2^30]");
+    SDT_CHECK_SUPPORTED(num_frames > 0 && num_frames <= (1 << 24), "unsupported size: window outside [1, 2^24] frames");
+    SDT_CHECK_ARG(repaired_per_frame != nullptr && starts != nullptr && workspace != nullptr && repaired_per_clip != nullptr, "null pointer");
+    SDT_CHECK_ARG(n_clips > 0 && n_clips <= n_frames && num_frames <= n_frames, "bad clip / window count");
+    SDT_CHECK_ARG(workspace_bytes >= sdt_clip_repair_workspace_bytes(n_frames), "workspace too small");
+    hipStream_t st = (hipStream_t)stream;
+    int64_t* prefix = (int64_t*)workspace;
+    hipLaunchKernelGGL(clip_repair_prefix_kernel, dim3(1), dim3(kThreads), 0, st, repaired_per_frame, n_frames, prefix);
+    hipLaunchKernelGGL(clip_repair_clip_counts_kernel, dim3((unsigned)cdiv64(n_clips, kThreads)), dim3(kThreads), 0, st, prefix, n_frames, starts,
+                       n_clips, num_frames, repaired_per_clip);
     SDT_LAUNCH_CHECK();
     return SDT_OK;
 }

@@ -5,6 +5,10 @@ times the same stages of the numpy contract models on the host.  One JSON line p
 events), keypoint-file reading and npz writing seconds and their share of the wall time, and the host models' seconds per stage.
 
     python tools/clip_builder_bench.py [--frames 18000] [--no-write] [--out profiles/r12_clip_builder_bench.jsonl]
+
+With --repair-max-gap G [--despike H KAPPA [FLOOR_PX]] the video also loses one finger joint for one frame every 131 frames, the repair
+stage of DESIGN.md section 26 runs, and the line (its ``repair`` kernel time next to ``flags`` of the same run, and the stage's counts)
+goes to profiles/r20_clip_repair_bench.jsonl instead.
 """
 import argparse
 import json
@@ -19,7 +23,7 @@ REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, REPO)
 
 
-def write_video(root, speaker, video, n, rate=48000):
+def write_video(root, speaker, video, n, rate=48000, dropouts=False):
     from scipy.io import wavfile
     g = np.random.Generator(np.random.PCG64(1))
     d = os.path.join(root, speaker, 'tmp', 'raw_pose_2d', video)
@@ -31,6 +35,8 @@ def write_video(root, speaker, video, n, rate=48000):
         a = (base + g.normal(0.0, 6.0, (3, 137))).astype(np.float32)
         if f % 997 == 500:
             a[:2, 30] = 0.0
+        if dropouts and f % 131 == 65:
+            a[:, 100] = 0.0  # OpenPose's (0, 0, 0) for a joint it did not detect
         np.save(os.path.join(d, '%s_%06d.npy' % (video, f)), a)
     samples = int(n / 15.0 * rate)
     wavfile.write(os.path.join(root, speaker, 'audio_full', video + '.wav'), rate,
@@ -82,17 +88,22 @@ def main():
     ap.add_argument("--frames", type=int, default=18000)
     ap.add_argument("--no-write", action="store_true")
     ap.add_argument("--skip-host", action="store_true")
-    ap.add_argument("--out", default=os.path.join(REPO, "profiles", "r12_clip_builder_bench.jsonl"))
-    a = ap.parse_args()
+    ap.add_argument("--out", default=None, help="default: profiles/r12_clip_builder_bench.jsonl, with the repair stage "
+                                                "profiles/r20_clip_repair_bench.jsonl")
     import torch
     from speechdrivestemplates_amd import clip_builder as cb
+    cb.add_repair_options(ap)
+    a = ap.parse_args()
+    rep = dict(repair_max_gap=a.repair_max_gap, despike=cb.despike_option(ap, a.despike))
+    if a.out is None:
+        a.out = os.path.join(REPO, "profiles", "r20_clip_repair_bench.jsonl" if a.repair_max_gap else "r12_clip_builder_bench.jsonl")
     with tempfile.TemporaryDirectory() as tmp:
         t0 = time.perf_counter()
-        write_video(tmp, "bench", "vid", a.frames)
+        write_video(tmp, "bench", "vid", a.frames, dropouts=bool(a.repair_max_gap))
         fixture_s = time.perf_counter() - t0
-        cb.build_clips(tmp, "bench", write=False)  # warm-up: library, allocator, page cache
+        cb.build_clips(tmp, "bench", write=False, **rep)  # warm-up: library, allocator, page cache
         t0 = time.perf_counter()
-        res = cb.build_clips(tmp, "bench", write=not a.no_write)
+        res = cb.build_clips(tmp, "bench", write=not a.no_write, **rep)
         total = time.perf_counter() - t0
         v = res['videos']['vid']
         k = v['timing']
@@ -102,7 +113,9 @@ def main():
                 "read_s": round(k['read_s'], 4), "write_s": round(k['write_s'], 4), "total_s": round(total, 4),
                 "file_io_share": round((k['read_s'] + k['write_s']) / total, 3), "write_fixture_s": round(fixture_s, 2),
                 "device": torch.cuda.get_device_name(0)}
-        if not a.skip_host:
+        if a.repair_max_gap:
+            line["repair_max_gap"], line["despike"], line["repair"] = a.repair_max_gap, rep["despike"], v["repair"]
+        if not a.skip_host and not a.repair_max_gap:  # (the host models below time the unrepaired stages)
             line["host_model"], n_p, n_a = host_models(tmp, "bench", "vid")
             assert n_p == n_a == len(res['table'])
     print(json.dumps(line), flush=True)
