@@ -946,7 +946,7 @@ def conv_input_grad(gy_cl, w, x_shape, stride, pad, norm_holder=None):
     if pack is not None and USE_STREAMK and not one_d:
         arr, n, gs = pack
         h = norm_holder
-        fuse = (h is not None and FUSE_BWD_STATS and h.y is not None and tuple(h.y.shape) == tuple(dx.shape)
+        fuse = (h is not None and FUSE_BWD_STATS and h.y is not None and h.y.dtype == torch.float32 and tuple(h.y.shape) == tuple(dx.shape)
                 and all((g.B * g.Ho * g.Wo if h.groups == 1 else g.Ho * g.Wo) >= 32 for g in gs))
         plan = _sk_plan(arr, n, -1, h.groups if fuse else 1, w.device)
         if plan is not None:
@@ -964,6 +964,7 @@ def conv_input_grad(gy_cl, w, x_shape, stride, pad, norm_holder=None):
         part = torch.empty((k,) + tuple(dx.shape), device=w.device, dtype=torch.float32) if k > 1 else None
         nb = None
         if (norm_holder is not None and FUSE_BWD_STATS and k == 1 and not one_d and Cout % 32 == 0 and norm_holder.y is not None
+                and norm_holder.y.dtype == torch.float32  # (a bf16 y with a gradient no bf16 kernel took: these kernels would read it as fp32)
                 and tuple(norm_holder.y.shape) == tuple(dx.shape) and dx.numel() * 4 < 2 ** 31 - 4  # (the epilogue's reads of y: 32-bit byte offsets)
                 and all((g.B * g.Ho * g.Wo if norm_holder.groups == 1 else g.Ho * g.Wo) >= 64 for g in gs)):
             h = norm_holder

@@ -4,7 +4,8 @@ copies live in HBM as bf16, products run on v_mfma_f32_32x32x16_bf16, accumulati
 The reference has no bf16 mode, so the tolerances are STATED here, per layer of the comparison:
   * one kernel against float64 on the SAME bf16-rounded operands: the products are exact in fp32, so what remains is the fp32 accumulation
     (1e-5 of max on the fp32 outputs: weight gradient, statistics) and ONE rounding of the output to bf16 (2^-8 = 3.9e-3 of each element's
-    magnitude -> 5e-3 of max).  That bar is the only one in THIS file; the norm and first-block kernels are held per element to half a bf16
+    magnitude -> 5e-3 of max; the conv kernels' y and dx are held PER ELEMENT to 2^-8 |ref| + 1e-5 max|ref|, which is never more, here and over
+    edge geometries in tests/test_bf16_conv_sweep_gpu.py); the norm and first-block kernels are held per element to half a bf16
     step, and bit for bit to their fp32-store instantiations, at the edge shapes of tests/test_edge_shapes_bf16_gpu.py;
   * the bf16 chain / train step against the fp32 one and against the float64 oracle: prediction 4e-2 of max, losses 2e-2, every gradient
     tensor with cosine similarity >= 0.97 to the float64 gradient and within 40 % of its max-norm.  (The round-3 mode that only rounded the
@@ -18,6 +19,7 @@ import torch
 import torch.nn.functional as F
 
 from oracle import sdt_oracle as O
+from test_edge_shapes_bf16_gpu import bf16_ratio
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
@@ -67,7 +69,8 @@ def test_bf16_conv_kernels_vs_float64_on_the_same_operands(ops, case, B):
     wr = w.double().requires_grad_(True)
     yr = F.conv2d(xr, wr, None, s, p)
     e = relmax(yd.float(), yr.permute(0, 2, 3, 1))
-    assert e <= 5e-3, (tag, "forward", e)
+    ey = bf16_ratio(yd, yr.permute(0, 2, 3, 1), 1e-5)  # per element: |got - ref| <= 2^-8 |ref| + 1e-5 max|ref| (<= 5e-3 max|ref|, the earlier bar)
+    assert ey <= 1.0, (tag, "forward", ey, e)
     ref_sums = torch.stack([yr.sum((2, 3)), (yr * yr).sum((2, 3))], -1)  # (B, Cout, 2): taken from the fp32 accumulators, before rounding
     es = relmax(sums.view(B, Cout, 2), ref_sums)
     assert es <= 2e-5, (tag, "statistics", es)
@@ -80,8 +83,10 @@ def test_bf16_conv_kernels_vs_float64_on_the_same_operands(ops, case, B):
     yr.backward(gy.double().permute(0, 3, 1, 2))
     edx = relmax(dxd.float(), xr.grad.permute(0, 2, 3, 1))
     edw = relmax(wd.grad, wr.grad)
-    print("  %s B=%d bf16 kernels vs float64 on the same operands: fwd %.2e (stats %.1e)  dX %.2e  dW %.2e" % (tag, B, e, es, edx, edw))
-    assert edx <= 5e-3, (tag, "dX", edx)
+    exr = bf16_ratio(dxd, xr.grad.permute(0, 2, 3, 1), 1e-5)
+    print("  %s B=%d bf16 kernels vs float64 on the same operands: fwd %.2e (stats %.1e)  dX %.2e  dW %.2e; per-element bf16 bar ratio fwd %.3f dX %.3f"
+          % (tag, B, e, es, edx, edw, ey, exr))
+    assert exr <= 1.0, (tag, "dX", exr, edx)
     assert edw <= 2e-5, (tag, "dW", edw)
 
 
