@@ -778,6 +778,28 @@ int sdt_clip_repair_clip_counts(const int32_t* repaired_per_frame, int64_t n_fra
                                 void* workspace, int64_t workspace_bytes, int32_t* repaired_per_clip, void* stream);
 
 /*
+ * Retiming of keypoints recorded at fps_num / fps_den frames per second onto the 15 fps grid, an opt-in stage in front of the repair
+ * stage (DESIGN.md section 27 is the contract).  Out of place: src (n_src, 3, 137) and present are read, src_t (n_out, 3, 137, same
+ * element type, another buffer) is written.  With D = 15 * fps_den and g = gcd(fps_num, D): n_out = (n_src - 1) * D / fps_num + 1, and
+ * output frame j has a = j * fps_num / D, r = j * fps_num % D (int64; no floating-point time) and reads row r / g of taps
+ * (n_phases = D / g rows of n_taps float64, designed on the host): tap i weighs source frame a + 1 - n_taps / 2 + i; a tap of weight 0
+ * takes part in nothing.  A source point is valid as in sdt_clip_repair_valid's valid0; a frame outside [0, n_src) is invalid.
+ * Per output point, over the non-zero taps with a valid source point in ascending i, in float64, every operation rounded on its own:
+ * num = sum h * v for x, y and the confidence, den = sum h; full = sum h over all non-zero taps of the row.  The point is valid iff
+ * den > 0 and den >= min_support * full, and is then num / den rounded once to the element type, else (0, 0, 0).
+ *   valid_t, taps_used (n_out, 137) uint8: the verdict and the number of taps that took part; present_t (n_out) uint8: a source frame
+ *   under a non-zero tap has a file; nearest_src (n_out) int32 = min(a + (2 r >= D), n_src - 1); counts (3 int64) = invalid source
+ *   points, source points with a non-finite x or y, invalid output points (integer block counts in workspace, summed by one workgroup).
+ * Supported: 1 <= fps_num <= 2^20, 1 <= fps_den <= 2^16, 1 <= fps_num / fps_den <= 240, n_phases <= 16384, n_taps even in [2, 32],
+ * n_src and n_out in [1, 2^30], min_support in (0, 1]; outside them the size query is negative and the entry point returns
+ * SDT_ERR_UNSUPPORTED before any launch.  No atomics: the same bits on every call.
+ */
+int64_t sdt_clip_retime_workspace_bytes(int64_t n_src, int64_t fps_num, int64_t fps_den, int n_phases, int n_taps);
+int sdt_clip_retime(int elem_bytes, const void* src, const void* present, int64_t n_src, int64_t fps_num, int64_t fps_den, const double* taps,
+                    int n_phases, int n_taps, double min_support, int64_t n_out, void* src_t, uint8_t* present_t, uint8_t* valid_t,
+                    uint8_t* taps_used, int32_t* nearest_src, int64_t* counts, void* workspace, int64_t workspace_bytes, void* stream);
+
+/*
  * Optimiser-side safeguards of the flat-buffer Adam (no counterpart in the reference): gradient-norm clipping as
  * torch.nn.utils.clip_grad_norm_(norm_type=2, error_if_nonfinite=False), a step that a non-finite gradient cannot poison, and an
  * exponential moving average of the parameters.  No atomics, no host read-back: hipGraph-capturable like the rest.

@@ -14,6 +14,8 @@ bit.  The models exist for the tests; ``build_clips`` has no CPU fallback.
     python -m speechdrivestemplates_amd.clip_builder --root DIR --speaker NAME [--start-frame 80] [--frames 64]
                                                      [--shoulder-chunks 1] [--no-write]
                                                      [--repair-max-gap G] [--despike H KAPPA [FLOOR_PX]]   (section 26, off by default)
+                                                     [--source-fps P[/Q]] [--retime nearest|linear|smooth] [--retime-min-support S]
+                                                                                    (section 27: keypoints not recorded at 15 fps)
 """
 import argparse
 import ctypes as C
@@ -322,6 +324,160 @@ def model_repair_summary(present, keep0, keep_r, rep, starts0, starts_r, per_cli
             'max_repaired_share': float(max(per_clip) / (num_frames * len(KEEP_121))) if len(per_clip) else 0.0}
 
 
+# ------------------------------------------------------------------------- keypoints recorded at any frame rate -> 15 fps (section 27)
+
+RETIME_MODES = ('nearest', 'linear', 'smooth')
+MAX_FPS_NUM, MAX_FPS_DEN, MAX_RATE, MAX_PHASES, MAX_TAPS = 1 << 20, 1 << 16, 240, 16384, 32  # the library's limits (sdt_clip_retime)
+
+
+def parse_fps(fps, name='fps'):
+    """an int, an (int, int) pair or a string 'P' / 'P/Q' -> (P, Q) in lowest terms; a ValueError names ``name``.  A float is refused:
+    29.97 is not 30000/1001, and the time map is exact integer arithmetic"""
+    if isinstance(fps, (float, np.floating)):
+        raise ValueError("%s must be an exact fraction, not the float %r: give it as 'P/Q', for example '30000/1001'" % (name, fps))
+    try:
+        if isinstance(fps, str):
+            parts = fps.strip().split('/')
+            if not 1 <= len(parts) <= 2 or not all(s.strip().isdigit() for s in parts):
+                raise TypeError
+            p, q = int(parts[0]), int(parts[1]) if len(parts) == 2 else 1
+        elif isinstance(fps, (tuple, list)):
+            if len(fps) != 2 or any(isinstance(v, (bool, float, np.floating)) or int(v) != v for v in fps):
+                raise TypeError
+            p, q = int(fps[0]), int(fps[1])
+        else:
+            if isinstance(fps, bool) or int(fps) != fps:
+                raise TypeError
+            p, q = int(fps), 1
+    except (TypeError, ValueError):
+        raise ValueError("%s must be an int, an (int, int) pair or a string 'P/Q' such as '30000/1001', not %r" % (name, fps)) from None
+    if p < 1 or q < 1:
+        raise ValueError('%s must be positive, not %d/%d' % (name, p, q))
+    c = gcd(p, q)
+    p, q = p // c, q // c
+    if p > MAX_FPS_NUM or q > MAX_FPS_DEN or p < q or p > MAX_RATE * q:
+        raise ValueError('%s = %d/%d: in lowest terms the numerator must be at most 2^20, the denominator at most 2^16 and the rate in '
+                         '[1, %d] fps' % (name, p, q, MAX_RATE))
+    if FPS * q // gcd(p, FPS * q) > MAX_PHASES:
+        raise ValueError('%s = %d/%d has %d phases against the %d fps grid (at most %d)' % (name, p, q, FPS * q // gcd(p, FPS * q), FPS, MAX_PHASES))
+    return p, q
+
+
+def retime_params(mode, min_support, names=('mode', 'min_support')):
+    """-> (mode, float(min_support)); a ValueError names the argument (``names``: what the caller calls them)"""
+    if mode not in RETIME_MODES:
+        raise ValueError('%s must be one of %s, not %r' % (names[0], ', '.join(RETIME_MODES), mode))
+    try:
+        s = float(min_support)
+    except (TypeError, ValueError):
+        s = float('nan')
+    if not 0.0 < s <= 1.0:
+        raise ValueError('%s must lie in (0, 1], not %r' % (names[1], min_support))
+    return mode, s
+
+
+def model_retime_plan(n_src, p, q):
+    """the time map, int64 only: output frame j sits at source time j * P / D frames, D = 15 * Q
+    -> dict(D, g, phases, n_out, a (n_out,), r, phase int64, nearest_src (n_out,) int32)"""
+    n_src, p, q = int(n_src), int(p), int(q)
+    if n_src < 1:
+        raise ValueError('n_src must be at least 1, not %d' % n_src)
+    d = FPS * q
+    g = gcd(p, d)
+    n_out = (n_src - 1) * d // p + 1
+    prod = np.arange(n_out, dtype=np.int64) * np.int64(p)
+    a, r = prod // d, prod % d
+    return {'D': d, 'g': g, 'phases': d // g, 'n_out': n_out, 'a': a, 'r': r, 'phase': r // g,
+            'nearest_src': np.minimum(a + (2 * r >= d), n_src - 1).astype(np.int32)}
+
+
+def model_retime_taps(p, q, mode):
+    """-> h (phases, L) float64, not normalised.  Tap i of phase phi weighs source frame a_j + i_lo + i, i_lo = 1 - L // 2, at distance
+    d = i_lo + i - t, t = (phi * g) / D.  nearest: (1, 0) if 2 r < D else (0, 1); linear: (1 - t, t); smooth: a raised cosine of half
+    width W = max(1, P / D) source frames, 0.5 * (1 + cos(pi * d / W)) for |d| < W, L = 2 * ceil(W)"""
+    from math import cos, pi
+    p, q = int(p), int(q)
+    if mode not in RETIME_MODES:
+        raise ValueError('mode must be one of %s, not %r' % (', '.join(RETIME_MODES), mode))
+    d = FPS * q
+    g = gcd(p, d)
+    phases = d // g
+    if mode == 'smooth':
+        width = max(1.0, p / d)
+        taps = 2 * max(1, -(-p // d))
+    else:
+        width, taps = 1.0, 2
+    if phases > MAX_PHASES or taps > MAX_TAPS:
+        raise ValueError('fps = %d/%d needs a tap table of %d x %d (at most %d x %d)' % (p, q, phases, taps, MAX_PHASES, MAX_TAPS))
+    i_lo = 1 - taps // 2
+    h = np.zeros((phases, taps), np.float64)
+    for phi in range(phases):
+        r = phi * g
+        t = float(r) / float(d)
+        if mode == 'nearest':
+            h[phi] = (1.0, 0.0) if 2 * r < d else (0.0, 1.0)
+        elif mode == 'linear':
+            h[phi] = (1.0 - t, t)
+        else:
+            for i in range(taps):
+                dist = float(i_lo + i) - t
+                if abs(dist) < width:
+                    h[phi, i] = 0.5 * (1.0 + cos(pi * dist / width))
+    return h
+
+
+def model_retime(src, present, p, q, mode='linear', min_support=0.75):
+    """src (n_src, 3, 137), present (n_src,) at P/Q fps -> dict(src_t (n_out, 3, 137) in src's dtype, present_t (n_out,) bool, valid_t
+    (n_out, 137) bool, taps_used (n_out, 137) uint8, nearest_src (n_out,) int32, counts (3,) int64 = invalid source points, source points
+    with a non-finite x or y, invalid output points).  Per output point, over the non-zero taps with a valid source point (``model_valid``;
+    a frame outside the video is invalid) in ascending order, in float64, every operation rounded on its own: num = sum h * v for x, y and
+    the confidence, den = sum h; full = sum h over all non-zero taps.  Valid iff den > 0 and den >= min_support * full: then num / den,
+    rounded once to src's dtype; else (0, 0, 0)"""
+    mode, min_support = retime_params(mode, min_support)
+    n_src = src.shape[0]
+    present = np.asarray(present, bool)
+    plan = model_retime_plan(n_src, p, q)
+    h = model_retime_taps(p, q, mode)
+    n_out, taps = plan['n_out'], h.shape[1]
+    i_lo = 1 - taps // 2
+    valid_src = model_valid(src, present)
+    s64 = src.astype(np.float64)
+    num = np.zeros((3, n_out, KP), np.float64)
+    den = np.zeros((n_out, KP), np.float64)
+    full = np.zeros(n_out, np.float64)
+    used = np.zeros((n_out, KP), np.uint8)
+    present_t = np.zeros(n_out, bool)
+    with np.errstate(invalid='ignore', over='ignore'):
+        for i in range(taps):
+            hi = h[plan['phase'], i]
+            nz = hi != 0
+            f = plan['a'] + (i_lo + i)
+            inside = nz & (f >= 0) & (f < n_src)
+            fs = np.where(inside, f, 0)
+            full = np.where(nz, full + hi, full)
+            present_t |= inside & present[fs]
+            ok = inside[:, None] & valid_src[fs]
+            for c in range(3):
+                prod = hi[:, None] * s64[fs, c, :]
+                num[c] = np.where(ok, np.where(used == 0, prod, num[c] + prod), num[c])
+            den = np.where(ok, den + hi[:, None], den)
+            used = used + ok.astype(np.uint8)
+        valid_t = (den > 0) & (den >= (np.float64(min_support) * full)[:, None])
+        out = np.zeros((n_out, 3, KP), src.dtype)
+        for c in range(3):
+            out[:, c, :] = np.where(valid_t, (num[c] / np.where(valid_t, den, 1.0)).astype(src.dtype), src.dtype.type(0))
+    x, y = src[:, 0, :], src[:, 1, :]
+    counts = np.array([(~valid_src).sum(), (~(np.isfinite(x) & np.isfinite(y))).sum(), (~valid_t).sum()], np.int64)
+    return {'src_t': out, 'present_t': present_t, 'valid_t': valid_t, 'taps_used': used, 'nearest_src': plan['nearest_src'], 'counts': counts}
+
+
+def model_retime_summary(rec, n_src, p, q, mode):
+    """the ``retime`` entry of a video's summary from the stage's records (exact integers)"""
+    counts = [int(v) for v in np.asarray(rec['counts']).reshape(-1)]
+    return {'source_frames': int(n_src), 'frames': int(len(rec['nearest_src'])), 'points_invalid_in': counts[0], 'points_invalid_out': counts[2],
+            'nonfinite_in': counts[1], 'mode': mode, 'P': int(p), 'Q': int(q), 'phases': FPS * int(q) // gcd(int(p), FPS * int(q))}
+
+
 # ----------------------------------------------------------------------------------------------------------------------- host I/O
 
 def _read_frames(video, dtype, pool):
@@ -358,10 +514,12 @@ def _read_wav(path):
     return int(sr), np.ascontiguousarray(a)
 
 
-def frame_image_paths(root_dir, speaker, video, start, num_frames):
-    """3_1:113-118, :187-189: the frame paths, from names alone"""
+def frame_image_paths(root_dir, speaker, video, start, num_frames, nearest_src=None):
+    """3_1:113-118, :187-189: the frame paths, from names alone.  ``nearest_src``: the source frame of each 15 fps frame of a retimed
+    video (section 27), so that the names are those of frames that were shot"""
     d = os.path.join(root_dir, speaker, 'frames', video)
-    return np.array([os.path.join(d, video + f"_{str(start + i).zfill(6)}.jpg") for i in range(num_frames)])
+    idx = [start + i if nearest_src is None else int(nearest_src[start + i]) for i in range(num_frames)]
+    return np.array([os.path.join(d, video + f"_{str(f).zfill(6)}.jpg") for f in idx])
 
 
 def clip_relpath(speaker, video, start, num_frames):
@@ -499,6 +657,41 @@ def device_repair(src, present, max_gap, despike=None, timer=None):
     return o
 
 
+def device_retime(src, present, fps, mode='linear', min_support=0.75, timer=None):
+    """the retime stage of one video (section 27).  src (n_src, 3, 137) and present (n_src,) uint8 on the device, recorded at ``fps``
+    (an int, an (int, int) pair or 'P/Q'; never a float), neither written -> dict(src_t (n_out, 3, 137), present_t (n_out,) uint8,
+    valid_t, taps_used (n_out, 137) uint8, nearest_src (n_out,) int32, counts (3,) int64: invalid source points, non-finite source
+    points, invalid output points; and P, Q, phases, mode).  Sizes outside the library's limits are a ValueError"""
+    import torch
+    from . import _lib
+    p, q = parse_fps(fps, 'fps')
+    mode, min_support = retime_params(mode, min_support)
+    lib = _lib.load()
+    dev, n_src = src.device, src.shape[0]
+    h = model_retime_taps(p, q, mode)
+    ws_bytes = lib.sdt_clip_retime_workspace_bytes(n_src, p, q, h.shape[0], h.shape[1])
+    if ws_bytes < 0:
+        raise ValueError('unsupported source frame count %d at fps = %d/%d (1 to 2^30 frames, before and after retiming)' % (n_src, p, q))
+    n_out = (n_src - 1) * (FPS * q) // p + 1
+    raw = torch.cuda.current_stream(dev).cuda_stream
+    taps = torch.from_numpy(h).to(dev)
+    ws = torch.empty(max(ws_bytes, 4), dtype=torch.uint8, device=dev)
+    o = {'src_t': torch.empty((n_out, 3, KP), dtype=src.dtype, device=dev), 'present_t': torch.empty(n_out, dtype=torch.uint8, device=dev),
+         'valid_t': torch.empty((n_out, KP), dtype=torch.uint8, device=dev), 'taps_used': torch.empty((n_out, KP), dtype=torch.uint8, device=dev),
+         'nearest_src': torch.empty(n_out, dtype=torch.int32, device=dev), 'counts': torch.empty(3, dtype=torch.int64, device=dev)}
+
+    def launch():
+        _check_size(lib.sdt_clip_retime(src.element_size(), _p(src), _p(present), n_src, p, q, _p(taps), h.shape[0], h.shape[1], min_support,
+                                        n_out, _p(o['src_t']), _p(o['present_t']), _p(o['valid_t']), _p(o['taps_used']), _p(o['nearest_src']),
+                                        _p(o['counts']), _p(ws), ws.numel(), raw))
+    if timer is not None:
+        timer.run('retime', launch)
+    else:
+        launch()
+    o.update(P=p, Q=q, phases=h.shape[0], mode=mode)
+    return o
+
+
 def device_repaired_per_clip(repaired_per_frame, starts, n_clips, num_frames):
     """-> (n_clips,) int32: the filled kept keypoints of each window"""
     import torch
@@ -584,12 +777,15 @@ def device_gather_audio(audio, a0, a1):
 
 
 def build_clips(root_dir, speaker, start_frame=80, num_frames=64, shoulder_chunks=1, scale_confidence=None, write=True, device='cuda',
-                repair_max_gap=0, despike=None):
+                repair_max_gap=0, despike=None, source_fps=None, retime='linear', retime_min_support=0.75):
     """-> {'videos': {name: summary}, 'table' (processed_137 order), 'timing'} and, with write=False, 'poses' (n_clips, num_frames, 3, 137),
     'audio' (n_clips, L_max), 'audio_lengths' (n_clips,) on the device in per-video, ascending-start order, with 'order' giving
     each table row's position in them.  ``repair_max_gap`` G >= 1 (with ``despike`` = (h, kappa, floor_px) or None) runs the repair
     stage of section 26 in front of the frame flags: each video's summary gains 'repair' and, with write=False, the result
-    'repaired_per_clip' (n_clips,) int32; with 0 nothing new is launched"""
+    'repaired_per_clip' (n_clips,) int32; with 0 nothing new is launched.  ``source_fps`` (an int, an (int, int) pair or 'P/Q') says the
+    keypoints were recorded at that rate and runs the retime stage of section 27 in front of everything else (``retime``: nearest, linear
+    or smooth; ``retime_min_support``): every count and index is then in 15 fps frames, each video's summary gains 'retime', and a clip's
+    ``imgs`` name the nearest source frames; with None, or a rate equal to 15, nothing new is launched"""
     import torch
     from . import _lib
     dev = torch.device(device)
@@ -603,6 +799,11 @@ def build_clips(root_dir, speaker, start_frame=80, num_frames=64, shoulder_chunk
         raise ValueError('despike needs repair_max_gap >= 1: a marked spike is repaired by the gap filling')
     if repair:
         repair_max_gap, despike = repair_params(repair_max_gap, despike)
+    fps_pq = None
+    if source_fps is not None:
+        fps_pq = parse_fps(source_fps, 'source_fps')
+        retime, retime_min_support = retime_params(retime, retime_min_support, ('retime', 'retime_min_support'))
+    retiming = fps_pq is not None and fps_pq[0] != FPS * fps_pq[1]
     plan = plan_clips(root_dir, speaker)
     first = next((p for v in plan for p in v['frames'].values()), None)
     if first is None:
@@ -632,6 +833,12 @@ def build_clips(root_dir, speaker, start_frame=80, num_frames=64, shoulder_chunk
             timer = _Timer(st)
             src = src_host.to(dev, non_blocking=True)
             present_dev = torch.from_numpy(present).to(dev)
+            rt = None
+            if retiming:  # from here on every frame index is a 15 fps frame
+                rt = device_retime(src, present_dev, fps_pq, retime, retime_min_support, timer)
+                src, present_dev, n = rt['src_t'], rt['present_t'], rt['src_t'].shape[0]
+                present = rt['present_t'].cpu().numpy()
+                nearest = rt['nearest_src'].cpu().numpy()
             if repair:
                 o0 = device_frame_stages(src, present_dev, start_frame, num_frames, shoulder_chunks)  # what the unrepaired tracks give
                 rep = device_repair(src, present_dev, repair_max_gap, despike, timer)
@@ -682,7 +889,8 @@ def build_clips(root_dir, speaker, start_frame=80, num_frames=64, shoulder_chunk
 
                 def save(i):
                     np.savez(os.path.join(base, table['pose_fn'].iloc[i]), pose=ph[i],
-                             imgs=frame_image_paths(root_dir, speaker, name, int(starts[i]), num_frames), audio=ah[i, :lh[i]])
+                             imgs=frame_image_paths(root_dir, speaker, name, int(starts[i]), num_frames, nearest if retiming else None),
+                             audio=ah[i, :lh[i]])
                 for f in [pool.submit(save, i) for i in range(n_clips)]:
                     f.result()
                 table.to_csv(os.path.join(base, 'tmp', 'intermediate_csv', 'tmp_%s.csv' % name), index=False)
@@ -699,6 +907,9 @@ def build_clips(root_dir, speaker, start_frame=80, num_frames=64, shoulder_chunk
                              'timing': {'kernel_ms': timer.totals(), 'read_s': t_read, 'write_s': t_write}}
             if repair:
                 summary[name]['repair'] = rep_summary
+            if retiming:
+                summary[name]['retime'] = model_retime_summary({'counts': rt['counts'].cpu().numpy(), 'nearest_src': nearest},
+                                                               video['n_frames'], fps_pq[0], fps_pq[1], retime)
     finally:
         pool.shutdown()
     import pandas as pd
@@ -728,6 +939,16 @@ def add_repair_options(ap):
                          'of its track and fill it like a gap (needs --repair-max-gap)')
 
 
+def add_retime_options(ap):
+    ap.add_argument('--source-fps', default=None, metavar='P[/Q]',
+                    help="the rate the keypoints were recorded at, as an exact fraction (25, 30, 30000/1001): they are retimed onto the 15 fps "
+                         "grid first (default: they are 15 fps already)")
+    ap.add_argument('--retime', choices=RETIME_MODES, default='linear',
+                    help='how: the nearest source frame, interpolation between the two neighbours, or a raised-cosine low-pass (with --source-fps)')
+    ap.add_argument('--retime-min-support', type=float, default=0.75, metavar='S',
+                    help='a retimed point is kept if the valid source points under its taps carry at least S of their weight (0 < S <= 1)')
+
+
 def despike_option(ap, values):
     if values is None:
         return None
@@ -746,9 +967,11 @@ def main(argv=None):
     ap.add_argument('--shoulder-chunks', type=int, default=1, help="chunks of the shoulder-distance mean (2_3's -np)")
     ap.add_argument('--no-write', action='store_true', help='build on the device and print the summary only')
     add_repair_options(ap)
+    add_retime_options(ap)
     a = ap.parse_args(argv)
     res = build_clips(a.root, a.speaker, start_frame=a.start_frame, num_frames=a.frames, shoulder_chunks=a.shoulder_chunks, write=not a.no_write,
-                      repair_max_gap=a.repair_max_gap, despike=despike_option(ap, a.despike))
+                      repair_max_gap=a.repair_max_gap, despike=despike_option(ap, a.despike), source_fps=a.source_fps, retime=a.retime,
+                      retime_min_support=a.retime_min_support)
     for name, s in res['videos'].items():
         k = s['timing']
         r = s.get('repair')
@@ -756,6 +979,11 @@ def main(argv=None):
                                       'largest repaired share of a clip %.4f'
                                       % (r['points_filled'], r['spikes'], r['spikes_unfilled'], r['frames_recovered'], r['missing_recovered'],
                                          r['clips_without_repair'], r['clips_with_repair'], r['max_repaired_share']))
+        t = s.get('retime')
+        if t is not None:
+            fixed += ', source %s fps: %d -> %d frames (%s, %d of %d retimed points invalid)' % (
+                '%d/%d' % (t['P'], t['Q']) if t['Q'] != 1 else '%d' % t['P'], t['source_frames'], t['frames'], t['mode'],
+                t['points_invalid_out'], t['frames'] * KP)
         print('video %s: %d frames, %d kept, %d dropped (%d missing), %d shoulder frames dropped by chunking, scalar %.9g, clips %d train / '
               '%d idle / %d dev (%.2f s reading, kernels %.3f ms, %.2f s writing)%s'
               % (name, s['frames'], s['kept'], s['dropped'], s['missing'], s['shoulder_dropped'], s['scalar'], s['clips']['train'],

@@ -12,8 +12,10 @@
 //   audio gather     per-clip slices with a length table
 //   repair (opt-in)  in front of the frame flags: per-point validity and spike marks, gap filling by interpolation into a second
 //                    buffer, the filled points per frame and per clip (integers)
+//   retime (opt-in)  in front of the repair: keypoints recorded at P/Q fps onto the 15 fps grid, an integer time map and host-designed
+//                    taps per phase, float64 sums over the valid source points, into a second buffer
 // Every floating-point operation is rounded on its own (contraction is off for the whole file) and no floating-point value is
-// accumulated with atomics, so every output is a fixed function of the inputs.  Contract and numbers: DESIGN.md sections 16 and 26.
+// accumulated with atomics, so every output is a fixed function of the inputs.  Contract and numbers: DESIGN.md sections 16, 26, 27.
 #include "common.h"
 
 #pragma clang fp contract(off)
@@ -448,6 +450,187 @@ __global__ void __launch_bounds__(kThreads) clip_repair_clip_counts_kernel(const
     out[c] = (s >= 0 && s + F <= n) ? (int32_t)(prefix[s + F] - prefix[s]) : -1;  // (the pack pass only emits windows inside the video)
 }
 
+// ------------------------------------------------------------------------------------------------------------------------- retime
+// Opt-in stage in front of the repair stage: keypoints recorded at P/Q fps are resampled onto the 15 fps grid.
+// Output frame j sits at source time j*P/D frames, D = 15*Q: a = j*P / D, r = j*P % D in int64 (no floating-point time), phase r / g,
+// g = gcd(P, D).  Row `phase` of the host-designed tap table weighs source frames a + i_lo .. a + i_lo + L - 1, i_lo = 1 - L/2; a tap of
+// weight 0 takes part in nothing.  Out of place: src is read, src_t is written.
+
+constexpr int kRetimeFrames = kFramesPerWave * (kThreads / 64);  // consecutive output frames of a workgroup
+constexpr int kRetimeMaxTaps = 32, kRetimeMaxPhases = 16384;
+
+struct RetimePlan {
+    int64_t d, g, n_out, blocks_out, blocks_src;
+};
+
+bool retime_plan(int64_t n_src, int64_t p, int64_t q, RetimePlan* rp) {
+    if (p < 1 || p > (1 << 20) || q < 1 || q > (1 << 16) || p < q || p > 240 * q) return false;  // 1 <= P/Q <= 240
+    if (n_src <= 0 || n_src > (1 << 30)) return false;
+    const int64_t d = 15 * q;
+    int64_t a = p, b = d;
+    while (b != 0) {
+        const int64_t t = a % b;
+        a = b;
+        b = t;
+    }
+    if (d / a > kRetimeMaxPhases) return false;
+    const int64_t n_out = (n_src - 1) * d / p + 1;  // below 2^51
+    if (n_out > (1 << 30)) return false;
+    rp->d = d;
+    rp->g = a;
+    rp->n_out = n_out;
+    rp->blocks_out = cdiv64(n_out, kRetimeFrames);
+    rp->blocks_src = cdiv64(n_src * kKp, kThreads);
+    return true;
+}
+
+// one workgroup per kRetimeFrames consecutive output frames: the time map of each frame once (16 threads), the tap rows of their
+// phases in LDS, then the frame-flags shape: a wave per kFramesPerWave frames, the lanes over the keypoints, every source row read
+// coalesced.  float64 products and sums in ascending tap order, each rounded on its own; one rounding to T.
+template <typename T>
+__global__ void __launch_bounds__(kThreads) clip_retime_kernel(const T* __restrict__ src, const uint8_t* __restrict__ present, int64_t n_src,
+                                                               int64_t p, int64_t d, int64_t g, const double* __restrict__ taps, int n_taps,
+                                                               double min_support, int64_t n_out, T* __restrict__ src_t,
+                                                               uint8_t* __restrict__ present_t, uint8_t* __restrict__ valid_t,
+                                                               uint8_t* __restrict__ taps_used, int32_t* __restrict__ nearest_src,
+                                                               int32_t* __restrict__ block_invalid) {
+    __shared__ double s_taps[kRetimeFrames * kRetimeMaxTaps];
+    __shared__ int64_t s_a[kRetimeFrames];
+    __shared__ int s_phase[kRetimeFrames], s_near[kRetimeFrames], s_count[kThreads / 64];
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    const int64_t j0 = (int64_t)blockIdx.x * kRetimeFrames;
+    if (threadIdx.x < kRetimeFrames) {
+        const int64_t j = j0 + threadIdx.x;
+        int64_t a = 0, r = 0;
+        if (j < n_out) {
+            const int64_t prod = j * p;  // below 2^50
+            a = prod / d;
+            r = prod - a * d;
+        }
+        s_a[threadIdx.x] = a;
+        s_phase[threadIdx.x] = (int)((int)r / (int)g);  // r < d <= 15 * 2^16
+        s_near[threadIdx.x] = 2 * r < d ? 0 : 1;
+    }
+    __syncthreads();
+    for (int e = threadIdx.x; e < kRetimeFrames * n_taps; e += kThreads) {
+        const int s = e / n_taps, i = e - s * n_taps;
+        s_taps[s * kRetimeMaxTaps + i] = taps[(int64_t)s_phase[s] * n_taps + i];  // phase < d / g = the table's rows
+    }
+    __syncthreads();
+    const int i_lo = 1 - n_taps / 2;
+    int invalid = 0;
+    for (int fg = 0; fg < kFramesPerWave; ++fg) {
+        const int s = w * kFramesPerWave + fg;
+        const int64_t j = j0 + s;
+        if (j < n_out) {  // uniform over the wave
+            const int64_t a = s_a[s];
+            const double* h = s_taps + s * kRetimeMaxTaps;
+            double full = 0.0;
+            bool any_present = false;
+            for (int i = 0; i < n_taps; ++i) {
+                if (h[i] == 0.0) continue;
+                full = full + h[i];
+                const int64_t f = a + i_lo + i;
+                any_present |= f >= 0 && f < n_src && present[f] != 0;
+            }
+            const double need = min_support * full;
+            for (int k0 = 0; k0 < kKp; k0 += 64) {  // (uniform: every lane reaches the ballot)
+                const int k = k0 + lane;
+                bool ok = false;
+                if (k < kKp) {
+                    double nx = 0.0, ny = 0.0, nc = 0.0, den = 0.0;
+                    int used = 0;
+                    for (int i = 0; i < n_taps; ++i) {
+                        const double hi = h[i];
+                        const int64_t f = a + i_lo + i;
+                        if (hi == 0.0 || f < 0 || f >= n_src) continue;  // uniform
+                        T x, y;
+                        if (!point_valid(src, present, f, k, &x, &y)) continue;
+                        const double px = hi * (double)x, py = hi * (double)y, pc = hi * (double)src[f * kFrameElems + 2 * kKp + k];
+                        nx = used ? nx + px : px;
+                        ny = used ? ny + py : py;
+                        nc = used ? nc + pc : pc;
+                        den = den + hi;
+                        ++used;
+                    }
+                    ok = den > 0.0 && den >= need;
+                    T* o = src_t + j * kFrameElems;
+                    o[k] = ok ? (T)(nx / den) : T(0);
+                    o[kKp + k] = ok ? (T)(ny / den) : T(0);
+                    o[2 * kKp + k] = ok ? (T)(nc / den) : T(0);
+                    valid_t[j * kKp + k] = ok ? 1 : 0;
+                    taps_used[j * kKp + k] = (uint8_t)used;
+                }
+                invalid += __popcll(__ballot(k < kKp && !ok));
+            }
+            if (lane == 0) {
+                present_t[j] = any_present ? 1 : 0;
+                const int64_t nf = a + s_near[s];
+                nearest_src[j] = (int32_t)(nf < n_src ? nf : n_src - 1);
+            }
+        }
+    }
+    if (lane == 0) s_count[w] = invalid;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        int tot = 0;
+        for (int i = 0; i < kThreads / 64; ++i) tot += s_count[i];
+        block_invalid[blockIdx.x] = tot;
+    }
+}
+
+// one thread per source point: block_counts[2b] = invalid points, [2b + 1] = points with a non-finite x or y, of the block's points
+template <typename T>
+__global__ void __launch_bounds__(kThreads) clip_retime_source_counts_kernel(const T* __restrict__ src, const uint8_t* __restrict__ present,
+                                                                             int64_t n_src, int32_t* __restrict__ block_counts) {
+    __shared__ int s_inv[kThreads / 64], s_nf[kThreads / 64];
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    const int64_t idx = (int64_t)blockIdx.x * kThreads + threadIdx.x;
+    bool inv = false, nf = false;
+    if (idx < n_src * kKp) {
+        T x, y;
+        inv = !point_valid(src, present, idx / kKp, (int)(idx % kKp), &x, &y);
+        nf = !(isfinite(x) && isfinite(y));
+    }
+    const int c_inv = __popcll(__ballot(inv)), c_nf = __popcll(__ballot(nf));
+    if (lane == 0) {
+        s_inv[w] = c_inv;
+        s_nf[w] = c_nf;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        int a = 0, b = 0;
+        for (int i = 0; i < kThreads / 64; ++i) {
+            a += s_inv[i];
+            b += s_nf[i];
+        }
+        block_counts[2 * (int64_t)blockIdx.x] = a;
+        block_counts[2 * (int64_t)blockIdx.x + 1] = b;
+    }
+}
+
+// one workgroup: counts[0] = invalid source points, [1] = non-finite source points, [2] = invalid output points (integers: any order)
+__global__ void __launch_bounds__(kThreads) clip_retime_total_kernel(const int32_t* __restrict__ block_invalid, int64_t blocks_out,
+                                                                     const int32_t* __restrict__ block_counts, int64_t blocks_src,
+                                                                     int64_t* __restrict__ counts) {
+    __shared__ int64_t s_sum[3][kThreads];
+    int64_t a = 0, b = 0, c = 0;
+    for (int64_t i = threadIdx.x; i < blocks_src; i += kThreads) {
+        a += block_counts[2 * i];
+        b += block_counts[2 * i + 1];
+    }
+    for (int64_t i = threadIdx.x; i < blocks_out; i += kThreads) c += block_invalid[i];
+    s_sum[0][threadIdx.x] = a;
+    s_sum[1][threadIdx.x] = b;
+    s_sum[2][threadIdx.x] = c;
+    __syncthreads();
+    if (threadIdx.x < 3) {
+        int64_t tot = 0;
+        for (int i = 0; i < kThreads; ++i) tot += s_sum[threadIdx.x][i];
+        counts[threadIdx.x] = tot;
+    }
+}
+
 struct ResPlan {
     int q_max, span_max, slots, tiles_per_block;
     int64_t lds;
@@ -658,6 +841,51 @@ extern "C" int sdt_clip_repair_clip_counts(const int32_t* repaired_per_frame, in
     hipLaunchKernelGGL(clip_repair_prefix_kernel, dim3(1), dim3(kThreads), 0, st, repaired_per_frame, n_frames, prefix);
     hipLaunchKernelGGL(clip_repair_clip_counts_kernel, dim3((unsigned)cdiv64(n_clips, kThreads)), dim3(kThreads), 0, st, prefix, n_frames, starts,
                        n_clips, num_frames, repaired_per_clip);
+    SDT_LAUNCH_CHECK();
+    return SDT_OK;
+}
+
+extern "C" int64_t sdt_clip_retime_workspace_bytes(int64_t n_src, int64_t fps_num, int64_t fps_den, int n_phases, int n_taps) {
+    RetimePlan rp;
+    if (!retime_plan(n_src, fps_num, fps_den, &rp)) return -1;
+    if ((int64_t)n_phases != rp.d / rp.g || n_taps < 2 || n_taps > kRetimeMaxTaps || (n_taps & 1)) return -1;
+    return (rp.blocks_out + 2 * rp.blocks_src) * (int64_t)sizeof(int32_t);  // the blocks' integer counts
+}
+
+extern "C" int sdt_clip_retime(int elem_bytes, const void* src, const void* present, int64_t n_src, int64_t fps_num, int64_t fps_den,
+                               const double* taps, int n_phases, int n_taps, double min_support, int64_t n_out, void* src_t,
+                               uint8_t* present_t, uint8_t* valid_t, uint8_t* taps_used, int32_t* nearest_src, int64_t* counts,
+                               void* workspace, int64_t workspace_bytes, void* stream) {
+    RetimePlan rp;
+    SDT_CHECK_SUPPORTED(retime_plan(n_src, fps_num, fps_den, &rp),
+                        "unsupported size: source frames outside [1, 2^30], fps_num outside [1, 2^20], fps_den outside [1, 2^16], a rate outside "
+                        "[1, 240] fps, more than 16384 phases or more than 2^30 output frames");
+    SDT_CHECK_SUPPORTED((int64_t)n_phases == rp.d / rp.g, "unsupported size: the tap table's rows are not the rate's 15 * fps_den / gcd phases");
+    SDT_CHECK_SUPPORTED(n_taps >= 2 && n_taps <= kRetimeMaxTaps && !(n_taps & 1), "unsupported size: taps per phase not even or outside [2, 32]");
+    SDT_CHECK_SUPPORTED(min_support > 0.0 && min_support <= 1.0, "unsupported size: min_support outside (0, 1]");
+    SDT_CHECK_ARG(elem_bytes == 4 || elem_bytes == 8, "elem_bytes must be 4 (float32 keypoints) or 8 (float64 keypoints)");
+    SDT_CHECK_ARG(src != nullptr && present != nullptr && taps != nullptr && src_t != nullptr && present_t != nullptr && valid_t != nullptr &&
+                      taps_used != nullptr && nearest_src != nullptr && counts != nullptr && workspace != nullptr,
+                  "null pointer");
+    SDT_CHECK_ARG(src != src_t, "the stage is out of place: src_t must not be src");
+    SDT_CHECK_ARG(n_out == rp.n_out, "n_out is not (n_src - 1) * 15 * fps_den / fps_num + 1");
+    SDT_CHECK_ARG(workspace_bytes >= (rp.blocks_out + 2 * rp.blocks_src) * (int64_t)sizeof(int32_t), "workspace too small");
+    hipStream_t st = (hipStream_t)stream;
+    int32_t* block_invalid = (int32_t*)workspace;
+    int32_t* block_counts = block_invalid + rp.blocks_out;
+    const dim3 grid_out((unsigned)rp.blocks_out), grid_src((unsigned)rp.blocks_src), block(kThreads);
+    if (elem_bytes == 4) {
+        hipLaunchKernelGGL((clip_retime_kernel<float>), grid_out, block, 0, st, (const float*)src, (const uint8_t*)present, n_src, fps_num, rp.d,
+                           rp.g, taps, n_taps, min_support, rp.n_out, (float*)src_t, present_t, valid_t, taps_used, nearest_src, block_invalid);
+        hipLaunchKernelGGL((clip_retime_source_counts_kernel<float>), grid_src, block, 0, st, (const float*)src, (const uint8_t*)present, n_src,
+                           block_counts);
+    } else {
+        hipLaunchKernelGGL((clip_retime_kernel<double>), grid_out, block, 0, st, (const double*)src, (const uint8_t*)present, n_src, fps_num, rp.d,
+                           rp.g, taps, n_taps, min_support, rp.n_out, (double*)src_t, present_t, valid_t, taps_used, nearest_src, block_invalid);
+        hipLaunchKernelGGL((clip_retime_source_counts_kernel<double>), grid_src, block, 0, st, (const double*)src, (const uint8_t*)present, n_src,
+                           block_counts);
+    }
+    hipLaunchKernelGGL(clip_retime_total_kernel, dim3(1), block, 0, st, block_invalid, rp.blocks_out, block_counts, rp.blocks_src, counts);
     SDT_LAUNCH_CHECK();
     return SDT_OK;
 }

@@ -9,6 +9,10 @@ events), keypoint-file reading and npz writing seconds and their share of the wa
 With --repair-max-gap G [--despike H KAPPA [FLOOR_PX]] the video also loses one finger joint for one frame every 131 frames, the repair
 stage of DESIGN.md section 26 runs, and the line (its ``repair`` kernel time next to ``flags`` of the same run, and the stage's counts)
 goes to profiles/r20_clip_repair_bench.jsonl instead.
+
+With --source-fps P[/Q] [--retime nearest|linear|smooth] the synthetic video is written at that rate (--frames source frames, the audio as
+long as they last), the retime stage of DESIGN.md section 27 runs in front of everything else, and the line (its ``retime`` kernel time
+next to ``flags`` of the same run, and the stage's counts) goes to profiles/r21_clip_retime_bench.jsonl instead.
 """
 import argparse
 import json
@@ -23,7 +27,7 @@ REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, REPO)
 
 
-def write_video(root, speaker, video, n, rate=48000, dropouts=False):
+def write_video(root, speaker, video, n, rate=48000, dropouts=False, fps=(15, 1)):
     from scipy.io import wavfile
     g = np.random.Generator(np.random.PCG64(1))
     d = os.path.join(root, speaker, 'tmp', 'raw_pose_2d', video)
@@ -38,7 +42,7 @@ def write_video(root, speaker, video, n, rate=48000, dropouts=False):
         if dropouts and f % 131 == 65:
             a[:, 100] = 0.0  # OpenPose's (0, 0, 0) for a joint it did not detect
         np.save(os.path.join(d, '%s_%06d.npy' % (video, f)), a)
-    samples = int(n / 15.0 * rate)
+    samples = n * fps[1] * rate // fps[0]
     wavfile.write(os.path.join(root, speaker, 'audio_full', video + '.wav'), rate,
                   np.round(g.uniform(-0.9, 0.9, (samples, 2)) * 32767).astype(np.int16))
 
@@ -89,17 +93,23 @@ def main():
     ap.add_argument("--no-write", action="store_true")
     ap.add_argument("--skip-host", action="store_true")
     ap.add_argument("--out", default=None, help="default: profiles/r12_clip_builder_bench.jsonl, with the repair stage "
-                                                "profiles/r20_clip_repair_bench.jsonl")
+                                                "profiles/r20_clip_repair_bench.jsonl, with --source-fps profiles/r21_clip_retime_bench.jsonl")
     import torch
     from speechdrivestemplates_amd import clip_builder as cb
     cb.add_repair_options(ap)
+    cb.add_retime_options(ap)
     a = ap.parse_args()
     rep = dict(repair_max_gap=a.repair_max_gap, despike=cb.despike_option(ap, a.despike))
+    fps = (15, 1)
+    if a.source_fps is not None:
+        fps = cb.parse_fps(a.source_fps, "--source-fps")
+        rep.update(source_fps=fps, retime=a.retime, retime_min_support=a.retime_min_support)
     if a.out is None:
-        a.out = os.path.join(REPO, "profiles", "r20_clip_repair_bench.jsonl" if a.repair_max_gap else "r12_clip_builder_bench.jsonl")
+        a.out = os.path.join(REPO, "profiles", "r21_clip_retime_bench.jsonl" if a.source_fps is not None else
+                             "r20_clip_repair_bench.jsonl" if a.repair_max_gap else "r12_clip_builder_bench.jsonl")
     with tempfile.TemporaryDirectory() as tmp:
         t0 = time.perf_counter()
-        write_video(tmp, "bench", "vid", a.frames, dropouts=bool(a.repair_max_gap))
+        write_video(tmp, "bench", "vid", a.frames, dropouts=bool(a.repair_max_gap) or a.source_fps is not None, fps=fps)
         fixture_s = time.perf_counter() - t0
         cb.build_clips(tmp, "bench", write=False, **rep)  # warm-up: library, allocator, page cache
         t0 = time.perf_counter()
@@ -107,7 +117,7 @@ def main():
         total = time.perf_counter() - t0
         v = res['videos']['vid']
         k = v['timing']
-        line = {"tool": "clip_builder_bench", "frames": a.frames, "dtype": res['dtype'], "sample_rate": v['sample_rate'], "channels": 2,
+        line = {"tool": "clip_builder_bench", "frames": v['frames'], "dtype": res['dtype'], "sample_rate": v['sample_rate'], "channels": 2,
                 "kept": v['kept'], "clips": len(res['table']), "write": not a.no_write,
                 "kernel_ms": {s: round(ms, 4) for s, ms in k['kernel_ms'].items()}, "kernel_ms_total": round(sum(k['kernel_ms'].values()), 4),
                 "read_s": round(k['read_s'], 4), "write_s": round(k['write_s'], 4), "total_s": round(total, 4),
@@ -115,7 +125,9 @@ def main():
                 "device": torch.cuda.get_device_name(0)}
         if a.repair_max_gap:
             line["repair_max_gap"], line["despike"], line["repair"] = a.repair_max_gap, rep["despike"], v["repair"]
-        if not a.skip_host and not a.repair_max_gap:  # (the host models below time the unrepaired stages)
+        if a.source_fps is not None:
+            line["source_fps"], line["retime_mode"], line["retime"] = "%d/%d" % fps, a.retime, v.get("retime")
+        if not a.skip_host and not a.repair_max_gap and a.source_fps is None:  # (the host models below time the plain 15 fps stages)
             line["host_model"], n_p, n_a = host_models(tmp, "bench", "vid")
             assert n_p == n_a == len(res['table'])
     print(json.dumps(line), flush=True)
