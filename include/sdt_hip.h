@@ -800,6 +800,41 @@ int sdt_clip_retime(int elem_bytes, const void* src, const void* present, int64_
                     uint8_t* taps_used, int32_t* nearest_src, int64_t* counts, void* workspace, int64_t workspace_bytes, void* stream);
 
 /*
+ * Audio activity gate, an opt-in stage between the window search and the gathers (DESIGN.md section 28 is the contract; no counterpart in
+ * the reference).  audio is the video's cut 16 kHz float32 track of n_samples; a hop is 160 samples, n_hops = n_samples / 160, the tail
+ * is ignored.  float64 with every operation rounded on its own, no floating-point atomics, integers after the threshold: the same bits
+ * on every call.
+ *   energy: e[h] = sum over the hop of d^2, d[n] = x[n] - (31/32) x[n-1], x[-1] = 0.  Lane l of 64 adds samples l, l + 64, l + 128
+ *     (below 160) of the hop in that order from +0.0, then the xor butterfly 32, 16, 8, 4, 2, 1.  flag (device int32; zeroed first) is set
+ *     when an e[h] is not finite.
+ *   mask: stats[0] = f = the energy of rank floor_pct * (n_hops - 1) / 100 in ascending order (an exact radix select on the bit patterns),
+ *     stats[1] = thr = f * margin if that is greater than abs_floor, else abs_floor (the product rounded once);
+ *     active_raw[h] = e[h] > thr (uint8).  n_hops = 0: stats = (0, 0).
+ *   smooth: (a) every maximal run of active hops shorter than min_run_hops becomes inactive; then (b) every maximal run of inactive hops
+ *     of length <= hang_hops with an active hop on both sides becomes active (runs that touch an end of the track are not filled).  0
+ *     disables a rule.  active must not alias active_raw.
+ *   windows: prefix (n_hops + 1 int32) = exclusive prefix sum of active.  For candidate window i (starts[i], ascending, with its audio
+ *     span a0[i], a1[i] in samples; a1 is clipped to n_samples, a0 below 0 to 0): n_h = the hops with 160 h >= a0 and 160 (h + 1) <= a1,
+ *     c = the active ones; counts_all (n_windows, 2 int32) = (c, n_h).  Kept iff n_h > 0 and 1000 c >= min_permille n_h (int64).
+ *     starts_kept, index_kept (the i) and counts_kept (n_kept, 2) list the kept windows in ascending order (capacity n_windows each);
+ *     n_kept (device int32) their number.
+ * Supported: 0 <= n_samples <= 160 * 2^24 + 159, 0 <= n_windows <= 2^30, floor_pct in [0, 50], min_run_hops and hang_hops in [0, 1024],
+ * min_permille in [1, 1000]; outside them sdt_clip_speech_workspace_bytes is negative and the entry points return SDT_ERR_UNSUPPORTED
+ * before any launch.  workspace: sdt_clip_speech_workspace_bytes(n_samples, n_windows) bytes serve every entry point; written before
+ * it is read.  No allocation; every index is checked against the sizes given.
+ */
+int64_t sdt_clip_speech_workspace_bytes(int64_t n_samples, int64_t n_windows);
+int sdt_clip_speech_energy(const float* audio, int64_t n_samples, double* energy, int32_t* flag, void* stream);
+int sdt_clip_speech_mask(const double* energy, int64_t n_hops, int floor_pct, double margin, double abs_floor, uint8_t* active_raw,
+                         double* stats, void* workspace, int64_t workspace_bytes, void* stream);
+int sdt_clip_speech_smooth(const uint8_t* active_raw, int64_t n_hops, int min_run_hops, int hang_hops, uint8_t* active, void* workspace,
+                           int64_t workspace_bytes, void* stream);
+int sdt_clip_speech_windows(const uint8_t* active, int64_t n_hops, int64_t n_samples, const int32_t* starts, const int64_t* a0,
+                            const int64_t* a1, int64_t n_windows, int min_permille, int32_t* prefix, int32_t* counts_all,
+                            int32_t* starts_kept, int32_t* index_kept, int32_t* counts_kept, int32_t* n_kept, void* workspace,
+                            int64_t workspace_bytes, void* stream);
+
+/*
  * Optimiser-side safeguards of the flat-buffer Adam (no counterpart in the reference): gradient-norm clipping as
  * torch.nn.utils.clip_grad_norm_(norm_type=2, error_if_nonfinite=False), a step that a non-finite gradient cannot poison, and an
  * exponential moving average of the parameters.  No atomics, no host read-back: hipGraph-capturable like the rest.

@@ -174,6 +174,11 @@ SIGNATURES = {
     "sdt_clip_repair_clip_counts": [_p, _i64, _p, _i64, _i, _p, _i64, _p, _p],
     "sdt_clip_retime_workspace_bytes": [_i64, _i64, _i64, _i, _i],  # (returns int64_t: restype set in load())
     "sdt_clip_retime": [_i, _p, _p, _i64, _i64, _i64, _p, _i, _i, C.c_double, _i64, _p, _p, _p, _p, _p, _p, _p, _i64, _p],
+    "sdt_clip_speech_workspace_bytes": [_i64, _i64],  # (returns int64_t: restype set in load())
+    "sdt_clip_speech_energy": [_p, _i64, _p, _p, _p],
+    "sdt_clip_speech_mask": [_p, _i64, _i, C.c_double, C.c_double, _p, _p, _p, _i64, _p],
+    "sdt_clip_speech_smooth": [_p, _i64, _i, _i, _p, _p, _i64, _p],
+    "sdt_clip_speech_windows": [_p, _i64, _i64, _p, _p, _p, _i64, _i, _p, _p, _p, _p, _p, _p, _p, _i64, _p],
     "sdt_grad_sumsq_partials": [],  # (returns int64_t: restype set in load())
     "sdt_optim_guard_pass_elems": [_i],  # (returns int64_t: restype set in load())
     "sdt_grad_sumsq_f64": [_p, _i64, _p, _p],
@@ -263,6 +268,7 @@ def load():
     lib.sdt_clip_resample_lds_bytes.restype = C.c_int64
     lib.sdt_clip_repair_workspace_bytes.restype = C.c_int64
     lib.sdt_clip_retime_workspace_bytes.restype = C.c_int64
+    lib.sdt_clip_speech_workspace_bytes.restype = C.c_int64
     lib.sdt_grad_sumsq_partials.restype = C.c_int64
     lib.sdt_optim_guard_pass_elems.restype = C.c_int64
     lib.sdt_long_report_workspace_bytes.restype = C.c_int64

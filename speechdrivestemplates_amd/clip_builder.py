@@ -16,6 +16,9 @@ bit.  The models exist for the tests; ``build_clips`` has no CPU fallback.
                                                      [--repair-max-gap G] [--despike H KAPPA [FLOOR_PX]]   (section 26, off by default)
                                                      [--source-fps P[/Q]] [--retime nearest|linear|smooth] [--retime-min-support S]
                                                                                     (section 27: keypoints not recorded at 15 fps)
+                                                     [--speech-gate PERMILLE] [--gate-margin-db DB] [--gate-floor-pct PCT] [--gate-abs-dbfs DBFS]
+                                                     [--gate-hang-ms MS] [--gate-min-ms MS]     (section 28: windows without audio activity dropped)
+    python -m speechdrivestemplates_amd.clip_builder --activity-report WAV [--gate-...]          (the gate's hop statistics of one wav)
 """
 import argparse
 import ctypes as C
@@ -478,6 +481,173 @@ def model_retime_summary(rec, n_src, p, q, mode):
             'nonfinite_in': counts[1], 'mode': mode, 'P': int(p), 'Q': int(q), 'phases': FPS * int(q) // gcd(int(p), FPS * int(q))}
 
 
+# ------------------------------------------------------------------------------- windows without audio activity dropped (section 28)
+
+HOP, PRE_EMPHASIS = 160, 31.0 / 32.0  # 10 ms at 16 kHz; a coefficient that is exact in binary, so its product with a float32 sample is exact
+MAX_HOPS, MAX_RUN_HOPS = 1 << 24, 1024  # the library's limits (sdt_clip_speech_*)
+GATE_DEFAULTS = {'margin_db': 12.0, 'floor_pct': 10, 'abs_dbfs': -60.0, 'hang_hops': 20, 'min_run_hops': 5}  # untuned: no real footage
+_GATE_INT = {'min_permille': (1, 1000), 'floor_pct': (0, 50), 'hang_hops': (0, MAX_RUN_HOPS), 'min_run_hops': (0, MAX_RUN_HOPS)}
+_GATE_REAL = {'margin_db': (0.0, 60.0), 'abs_dbfs': (-120.0, 0.0)}
+
+
+def speech_gate_params(gate):
+    """a dict with 'min_permille' and any of margin_db, floor_pct, abs_dbfs, hang_hops, min_run_hops (GATE_DEFAULTS for the rest) -> all six
+    as ints / floats; a ValueError names what is unknown, missing or out of range"""
+    if not isinstance(gate, dict):
+        raise ValueError("speech_gate is None or a dict such as {'min_permille': 500}, not %r" % (gate,))
+    unknown = sorted(set(gate) - set(_GATE_INT) - set(_GATE_REAL))
+    if unknown:
+        raise ValueError('speech_gate: unknown key %s (known: %s)' % (', '.join(map(repr, unknown)), ', '.join(sorted(set(_GATE_INT) | set(_GATE_REAL)))))
+    if 'min_permille' not in gate:
+        raise ValueError('speech_gate needs min_permille (1..1000): the share of active hops, in thousandths, a window must reach')
+    full = dict(GATE_DEFAULTS)
+    full.update(gate)
+    out = {}
+    for k, (lo, hi) in _GATE_INT.items():
+        v = full[k]
+        if isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, float, np.integer, np.floating)) or not np.isfinite(v) or int(v) != v \
+                or not lo <= int(v) <= hi:
+            raise ValueError('speech_gate %s must be an integer in %d..%d, not %r' % (k, lo, hi, v))
+        out[k] = int(v)
+    for k, (lo, hi) in _GATE_REAL.items():
+        v = full[k]
+        if isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, float, np.integer, np.floating)) or not np.isfinite(v) \
+                or not lo <= float(v) <= hi:
+            raise ValueError('speech_gate %s must be finite and in %g..%g, not %r' % (k, lo, hi, v))
+        out[k] = float(v)
+    return out
+
+
+def gate_ms_to_hops(ms, name):
+    """a duration in ms that is a whole multiple of the 10 ms hop -> hops; a ValueError names the argument"""
+    if isinstance(ms, (bool, np.bool_)) or not isinstance(ms, (int, float, np.integer, np.floating)) or not np.isfinite(ms) or int(ms) != ms \
+            or int(ms) < 0 or int(ms) % 10:
+        raise ValueError('%s must be a whole, non-negative multiple of 10 ms (one hop), not %r' % (name, ms))
+    return int(ms) // 10
+
+
+def gate_constants(params):
+    """-> (M, A): the margin as a power ratio and the absolute floor as the energy of one hop, python floats (passed to the device as doubles)"""
+    return 10 ** (params['margin_db'] / 10), HOP * 10 ** (params['abs_dbfs'] / 10)
+
+
+def model_hop_energy(x):
+    """x (N,) float32 -> e (N // 160,) float64: the sum over each hop of (x[n] - (31/32) x[n-1])^2, x[-1] = 0, in float64, every operation
+    rounded on its own, in the order of the kernel: lane l of 64 adds samples l, l + 64, l + 128 (below 160) from +0.0, then the xor
+    butterfly 32, 16, 8, 4, 2, 1"""
+    x64 = np.asarray(x, np.float32).astype(np.float64)
+    n_hops = len(x64) // HOP
+    lanes = np.zeros((n_hops, 64), np.float64)
+    if n_hops == 0:
+        return lanes[:, 0].copy()
+    with np.errstate(invalid='ignore', over='ignore'):
+        d = x64 - PRE_EMPHASIS * np.concatenate([[0.0], x64[:-1]])
+        sq = (d * d)[:n_hops * HOP].reshape(n_hops, HOP)
+        for j in range(0, HOP, 64):
+            w = min(64, HOP - j)
+            lanes[:, :w] = lanes[:, :w] + sq[:, j:j + w]
+        idx = np.arange(64)
+        for o in (32, 16, 8, 4, 2, 1):
+            lanes = lanes + lanes[:, idx ^ o]
+    return lanes[:, 0].copy()
+
+
+def model_floor(energy, floor_pct):
+    """the energy of rank (floor_pct * (H - 1)) // 100 in ascending order of the bit patterns (energies are not negative, so that is the
+    order of the values); None without a hop"""
+    e = np.ascontiguousarray(energy, np.float64)
+    if len(e) == 0:
+        return None
+    k = (int(floor_pct) * (len(e) - 1)) // 100
+    return float(np.sort(e.view(np.uint64))[k:k + 1].view(np.float64)[0])
+
+
+def model_mask(energy, floor, margin, abs_floor):
+    """-> (active_raw (H,) bool, thr): thr = floor * margin (rounded once) where that is greater than abs_floor, else abs_floor"""
+    with np.errstate(invalid='ignore', over='ignore'):
+        scaled = np.float64(floor) * np.float64(margin)
+        thr = float(scaled) if scaled > abs_floor else float(abs_floor)
+        return np.asarray(energy, np.float64) > thr, thr
+
+
+def _nearest_marks(mark):
+    """mark (H,) bool -> (the last marked index at or before h or -1, the first at or after h or H)"""
+    n = len(mark)
+    idx = np.arange(n, dtype=np.int64)
+    prev = np.maximum.accumulate(np.where(mark, idx, -1)) if n else idx
+    nxt = np.minimum.accumulate(np.where(mark, idx, n)[::-1])[::-1] if n else idx
+    return prev, nxt
+
+
+def model_smooth(active_raw, min_run_hops, hang_hops):
+    """(a) every maximal run of active hops shorter than min_run_hops becomes inactive; then (b) every maximal run of inactive hops of at
+    most hang_hops with an active hop on both sides becomes active.  0 disables a rule.  Integers only"""
+    m = np.asarray(active_raw, bool)
+    n = len(m)
+    prev, nxt = _nearest_marks(~m)
+    opened = m & (nxt - prev - 1 >= int(min_run_hops))
+    prev, nxt = _nearest_marks(opened)
+    return opened | ((prev >= 0) & (nxt < n) & (nxt - prev - 1 <= int(hang_hops)))
+
+
+def model_window_counts(active, n_samples, offsets):
+    """offsets [(a0, a1)] in samples -> (n, 2) int32 of (c, n_h): the hops wholly inside [a0, min(a1, N)) (a0 below 0 counts as 0) and the
+    active ones among them, through an integer prefix sum"""
+    pre = np.concatenate([[0], np.cumsum(np.asarray(active, bool).astype(np.int64))])
+    n_hops = len(pre) - 1
+    out = np.zeros((len(offsets), 2), np.int32)
+    for i, (a0, a1) in enumerate(offsets):
+        h0 = -(-max(int(a0), 0) // HOP)
+        h1 = min(max(min(int(a1), int(n_samples)), 0) // HOP, n_hops)
+        if h1 > h0:
+            out[i] = (pre[h1] - pre[h0], h1 - h0)
+    return out
+
+
+def model_windows_kept(counts, min_permille):
+    """(n, 2) of (c, n_h) -> (n,) bool: n_h > 0 and 1000 c >= min_permille n_h, in int64"""
+    c = np.asarray(counts, np.int64).reshape(-1, 2)
+    return (c[:, 1] > 0) & (1000 * c[:, 0] >= int(min_permille) * c[:, 1])
+
+
+def _db(v):
+    return float(10.0 * np.log10(v)) if v is not None and v > 0 else float('-inf') if v is not None else None
+
+
+def speech_gate_summary(n_hops, n_raw, n_active, floor, thr, n_windows, n_kept):
+    """the ``speech_gate`` entry of a video's summary (floor_db / thr_db: 10 log10 on the host, for reading only)"""
+    share = n_active / n_hops if n_hops else 0.0
+    note = None
+    if n_hops and not 0.05 <= share <= 0.95:
+        note = ('%.1f %% of the hops are active: ' % (100 * share)) + (
+            'the floor may lie inside the speech (see floor_pct, abs_dbfs)' if share < 0.05 else 'the gate drops next to nothing here')
+    return {'hops': int(n_hops), 'active_raw': int(n_raw), 'active': int(n_active), 'floor_db': _db(floor), 'thr_db': _db(thr) if n_hops else None,
+            'windows': int(n_windows), 'kept': int(n_kept), 'active_share': share, 'note': note, 'clips': 'clips %d -> %d' % (n_windows, n_kept)}
+
+
+def model_speech_gate(x, starts, start_frame, num_frames, gate):
+    """the whole stage on one video's cut 16 kHz track x and the window starts the keypoints allow -> dict(energy, floor, thr, active_raw,
+    active, offsets, counts_all, kept (bool per start), starts, counts, summary)"""
+    p = speech_gate_params(gate)
+    margin, abs_floor = gate_constants(p)
+    x = np.asarray(x, np.float32)
+    e = model_hop_energy(x)
+    if not np.isfinite(e).all():
+        raise ValueError('non-finite hop energy')
+    floor = model_floor(e, p['floor_pct'])
+    if len(e):
+        raw, thr = model_mask(e, floor, margin, abs_floor)
+    else:
+        raw, thr = np.zeros(0, bool), None
+    active = model_smooth(raw, p['min_run_hops'], p['hang_hops'])
+    offs = [audio_offsets(int(s), start_frame, num_frames) for s in starts]
+    counts = model_window_counts(active, len(x), offs)
+    kept = model_windows_kept(counts, p['min_permille'])
+    return {'energy': e, 'floor': floor, 'thr': thr, 'active_raw': raw, 'active': active, 'offsets': offs, 'counts_all': counts, 'kept': kept,
+            'starts': np.asarray(starts, np.int64)[kept], 'counts': counts[kept],
+            'summary': speech_gate_summary(len(e), raw.sum(), active.sum(), floor, thr, len(offs), kept.sum())}
+
+
 # ----------------------------------------------------------------------------------------------------------------------- host I/O
 
 def _read_frames(video, dtype, pool):
@@ -776,8 +946,93 @@ def device_gather_audio(audio, a0, a1):
     return out, lengths
 
 
+def _speech_workspace(lib, n_samples, n_windows, dev):
+    import torch
+    ws_bytes = lib.sdt_clip_speech_workspace_bytes(int(n_samples), int(n_windows))
+    if ws_bytes < 0:
+        raise ValueError('unsupported track length / window count (%d samples, %d windows; at most 160 * 2^24 + 159 and 2^30)' % (n_samples, n_windows))
+    return torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+
+
+def device_hop_energy(audio):
+    """audio (N,) float32 on the device -> (e (N // 160,) float64, flag (1,) int32: an energy is not finite); ``model_hop_energy``"""
+    import torch
+    from . import _lib
+    lib = _lib.load()
+    if audio.dtype != torch.float32 or audio.dim() != 1 or not audio.is_contiguous():
+        raise ValueError('the track must be a contiguous 1-d float32 tensor')
+    n = audio.numel()
+    if lib.sdt_clip_speech_workspace_bytes(n, 0) < 0:
+        raise ValueError('unsupported track length %d (at most 160 * 2^24 + 159 samples)' % n)
+    e = torch.empty(n // HOP, dtype=torch.float64, device=audio.device)
+    flag = torch.empty(1, dtype=torch.int32, device=audio.device)
+    _check_size(lib.sdt_clip_speech_energy(_p(audio), n, _p(e), _p(flag), torch.cuda.current_stream(audio.device).cuda_stream))
+    return e, flag
+
+
+def device_speech_mask(energy, floor_pct, margin, abs_floor):
+    """-> (active_raw (H,) uint8, stats (2,) float64 = floor, thr); ``model_floor`` and ``model_mask``"""
+    import torch
+    from . import _lib
+    lib = _lib.load()
+    dev, h = energy.device, energy.numel()
+    ws = _speech_workspace(lib, min(h, MAX_HOPS) * HOP, 0, dev)
+    raw = torch.empty(h, dtype=torch.uint8, device=dev)
+    stats = torch.empty(2, dtype=torch.float64, device=dev)
+    _check_size(lib.sdt_clip_speech_mask(_p(energy), h, int(floor_pct), float(margin), float(abs_floor), _p(raw), _p(stats), _p(ws), ws.numel(),
+                                         torch.cuda.current_stream(dev).cuda_stream))
+    return raw, stats
+
+
+def device_speech_smooth(active_raw, min_run_hops, hang_hops):
+    """-> active (H,) uint8; ``model_smooth``"""
+    import torch
+    from . import _lib
+    lib = _lib.load()
+    dev, h = active_raw.device, active_raw.numel()
+    ws = _speech_workspace(lib, min(h, MAX_HOPS) * HOP, 0, dev)
+    out = torch.empty(h, dtype=torch.uint8, device=dev)
+    _check_size(lib.sdt_clip_speech_smooth(_p(active_raw), h, int(min_run_hops), int(hang_hops), _p(out), _p(ws), ws.numel(),
+                                           torch.cuda.current_stream(dev).cuda_stream))
+    return out
+
+
+def device_speech_windows(active, n_samples, starts, offsets, min_permille):
+    """active (H,) uint8 and starts (>= n int32, ascending) on the device, offsets [(a0, a1)] of the n candidate windows on the host ->
+    dict(prefix (H + 1,), counts_all (n, 2), starts (n,), index (n,), counts (n, 2) int32: the first n_kept rows hold the kept windows,
+    n_kept (1,) int32); ``model_window_counts`` and ``model_windows_kept``"""
+    import torch
+    from . import _lib
+    lib = _lib.load()
+    dev, h, n = active.device, active.numel(), len(offsets)
+    if h != int(n_samples) // HOP:
+        raise ValueError('%d hops do not belong to a track of %d samples' % (h, n_samples))
+    ws = _speech_workspace(lib, n_samples, n, dev)
+    a = torch.tensor([[int(a0), int(a1)] for a0, a1 in offsets], dtype=torch.int64).reshape(n, 2).t().contiguous().to(dev)
+    o = {'prefix': torch.empty(h + 1, dtype=torch.int32, device=dev), 'counts_all': torch.empty((n, 2), dtype=torch.int32, device=dev),
+         'starts': torch.empty(n, dtype=torch.int32, device=dev), 'index': torch.empty(n, dtype=torch.int32, device=dev),
+         'counts': torch.empty((n, 2), dtype=torch.int32, device=dev), 'n_kept': torch.empty(1, dtype=torch.int32, device=dev)}
+    _check_size(lib.sdt_clip_speech_windows(_p(active), h, int(n_samples), _p(starts), _p(a[0]) if n else None, _p(a[1]) if n else None, n,
+                                            int(min_permille), _p(o['prefix']), _p(o['counts_all']), _p(o['starts']), _p(o['index']),
+                                            _p(o['counts']), _p(o['n_kept']), _p(ws), ws.numel(), torch.cuda.current_stream(dev).cuda_stream))
+    return o
+
+
+def device_speech_gate(audio, starts, offsets, params, timer=None):
+    """the whole stage of section 28 on one video: audio (N,) float32 and starts (int32, ascending) on the device, offsets the windows'
+    audio spans -> dict(energy, flag, active_raw, stats, active and ``device_speech_windows``' entries)"""
+    margin, abs_floor = gate_constants(params)
+    run = timer.run if timer is not None else (lambda stage, fn: fn())
+    o = {}
+    run('gate_energy', lambda: o.update(zip(('energy', 'flag'), device_hop_energy(audio))))
+    run('gate_mask', lambda: o.update(zip(('active_raw', 'stats'), device_speech_mask(o['energy'], params['floor_pct'], margin, abs_floor))))
+    run('gate_smooth', lambda: o.__setitem__('active', device_speech_smooth(o['active_raw'], params['min_run_hops'], params['hang_hops'])))
+    run('gate_windows', lambda: o.update(device_speech_windows(o['active'], audio.numel(), starts, offsets, params['min_permille'])))
+    return o
+
+
 def build_clips(root_dir, speaker, start_frame=80, num_frames=64, shoulder_chunks=1, scale_confidence=None, write=True, device='cuda',
-                repair_max_gap=0, despike=None, source_fps=None, retime='linear', retime_min_support=0.75):
+                repair_max_gap=0, despike=None, source_fps=None, retime='linear', retime_min_support=0.75, speech_gate=None):
     """-> {'videos': {name: summary}, 'table' (processed_137 order), 'timing'} and, with write=False, 'poses' (n_clips, num_frames, 3, 137),
     'audio' (n_clips, L_max), 'audio_lengths' (n_clips,) on the device in per-video, ascending-start order, with 'order' giving
     each table row's position in them.  ``repair_max_gap`` G >= 1 (with ``despike`` = (h, kappa, floor_px) or None) runs the repair
@@ -785,7 +1040,11 @@ def build_clips(root_dir, speaker, start_frame=80, num_frames=64, shoulder_chunk
     'repaired_per_clip' (n_clips,) int32; with 0 nothing new is launched.  ``source_fps`` (an int, an (int, int) pair or 'P/Q') says the
     keypoints were recorded at that rate and runs the retime stage of section 27 in front of everything else (``retime``: nearest, linear
     or smooth; ``retime_min_support``): every count and index is then in 15 fps frames, each video's summary gains 'retime', and a clip's
-    ``imgs`` name the nearest source frames; with None, or a rate equal to 15, nothing new is launched"""
+    ``imgs`` name the nearest source frames; with None, or a rate equal to 15, nothing new is launched.  ``speech_gate`` (a dict with
+    'min_permille' and optionally margin_db, floor_pct, abs_dbfs, hang_hops, min_run_hops) runs the audio activity gate of section 28
+    between the window search and the gathers: a window stays a clip only if that share of the 10 ms hops inside its audio span lie
+    above the track's noise floor; each video's summary gains 'speech_gate', the result 'speech_counts' (n_clips, 2) int32 of (active
+    hops, hops) with write=False, and tmp/activity/<video>.npz is written with write=True; with None nothing new is launched"""
     import torch
     from . import _lib
     dev = torch.device(device)
@@ -804,6 +1063,7 @@ def build_clips(root_dir, speaker, start_frame=80, num_frames=64, shoulder_chunk
         fps_pq = parse_fps(source_fps, 'source_fps')
         retime, retime_min_support = retime_params(retime, retime_min_support, ('retime', 'retime_min_support'))
     retiming = fps_pq is not None and fps_pq[0] != FPS * fps_pq[1]
+    gate = None if speech_gate is None else speech_gate_params(speech_gate)
     plan = plan_clips(root_dir, speaker)
     first = next((p for v in plan for p in v['frames'].values()), None)
     if first is None:
@@ -817,9 +1077,11 @@ def build_clips(root_dir, speaker, start_frame=80, num_frames=64, shoulder_chunk
     if write:
         os.makedirs(os.path.join(base, 'clips', 'npz'), exist_ok=True)
         os.makedirs(os.path.join(base, 'tmp', 'intermediate_csv'), exist_ok=True)
+        if gate is not None:
+            os.makedirs(os.path.join(base, 'tmp', 'activity'), exist_ok=True)
     st = torch.cuda.current_stream(dev)
     pool = ThreadPoolExecutor(max_workers=MAX_READ_THREADS)
-    summary, tables, all_poses, all_audio, all_len, all_rep = {}, [], [], [], [], []
+    summary, tables, all_poses, all_audio, all_len, all_rep, all_gate = {}, [], [], [], [], [], []
     t_all = time.perf_counter()
     try:
         for video in plan:
@@ -859,24 +1121,34 @@ def build_clips(root_dir, speaker, start_frame=80, num_frames=64, shoulder_chunk
                                  % (video['dir'], float(mean), n_kept, shoulder_chunks))
             scalar = float(OLIVER_SHOULDER * 1.0 / mean)
             starts = o['starts'][:n_clips].cpu().numpy().astype(np.int64)
+            starts_dev, n_windows = o['starts'], n_clips  # (the windows the keypoints allow)
             holder = {}
-            timer.run('gather_poses', lambda: holder.__setitem__('poses', device_gather_poses(src, o['starts'], n_clips, num_frames, scalar, scale_conf)))
+            if gate is None:
+                timer.run('gather_poses', lambda: holder.__setitem__('poses', device_gather_poses(src, o['starts'], n_clips, num_frames, scalar, scale_conf)))
             cut = source_cut(start_frame, sr_in)
             raw_pcm = upload_pcm(pcm, dev)
             timer.run('pcm', lambda: holder.__setitem__('mono', device_pcm_to_mono(pcm, cut, dev, raw_pcm)))
             timer.run('resample', lambda: holder.__setitem__('audio', device_resample(holder['mono'], sr_in)))
             offs = [audio_offsets(int(s), start_frame, num_frames) for s in starts]
+            if gate is not None:  # the gate reads the resampled track, so the poses are gathered behind it, for the kept windows only
+                sg = device_speech_gate(holder['audio'], o['starts'], offs, gate, timer)
+                n_clips = int(sg['n_kept'].item())  # (synchronises)
+                if int(sg['flag'].item()):
+                    raise ValueError('%s: non-finite audio samples (a hop energy is not finite)' % video['wav'])
+                index = sg['index'][:n_clips].cpu().numpy()
+                starts_all, starts, offs, starts_dev = starts, starts[index], [offs[i] for i in index], sg['starts']
+                timer.run('gather_poses', lambda: holder.__setitem__('poses', device_gather_poses(src, starts_dev, n_clips, num_frames, scalar, scale_conf)))
             timer.run('gather_audio', lambda: holder.__setitem__('clips', device_gather_audio(holder['audio'], [a for a, _ in offs], [b for _, b in offs])))
             torch.cuda.synchronize(dev)
             poses, (audio, lengths) = holder['poses'], holder['clips']
             n_present = int(present.sum())
             rep_summary = None
             if repair:
-                per_clip = device_repaired_per_clip(rep['repaired_per_frame'], o['starts'], n_clips, num_frames)
+                per_clip = device_repaired_per_clip(rep['repaired_per_frame'], starts_dev, n_clips, num_frames)
                 host = {k: rep[k].cpu().numpy() for k in ('filled', 'spike', 'present_r')}
                 n0 = int(o0['n_clips'].item())
                 rep_summary = model_repair_summary(present, o0['keep'].cpu().numpy(), o['keep'].cpu().numpy(), host,
-                                                   range(n0), starts, per_clip.cpu().numpy(), num_frames)
+                                                   range(n0), range(n_windows), per_clip.cpu().numpy(), num_frames)
                 n_present = int(host['present_r'].sum())  # (the files and the frames the stage gave back)
                 if not write:
                     all_rep.append(per_clip)
@@ -894,6 +1166,10 @@ def build_clips(root_dir, speaker, start_frame=80, num_frames=64, shoulder_chunk
                 for f in [pool.submit(save, i) for i in range(n_clips)]:
                     f.result()
                 table.to_csv(os.path.join(base, 'tmp', 'intermediate_csv', 'tmp_%s.csv' % name), index=False)
+                if gate is not None:
+                    np.savez(os.path.join(base, 'tmp', 'activity', name + '.npz'), energy=sg['energy'].cpu().numpy(),
+                             active_raw=sg['active_raw'].cpu().numpy(), active=sg['active'].cpu().numpy(), starts_all=starts_all,
+                             counts_all=sg['counts_all'].cpu().numpy())
                 t_write = time.perf_counter() - t0
             else:
                 all_poses.append(poses)
@@ -907,6 +1183,13 @@ def build_clips(root_dir, speaker, start_frame=80, num_frames=64, shoulder_chunk
                              'timing': {'kernel_ms': timer.totals(), 'read_s': t_read, 'write_s': t_write}}
             if repair:
                 summary[name]['repair'] = rep_summary
+            if gate is not None:
+                n_hops = sg['energy'].numel()
+                floor, thr = (float(v) for v in sg['stats'].cpu().numpy()) if n_hops else (None, None)
+                summary[name]['speech_gate'] = speech_gate_summary(n_hops, int(sg['active_raw'].sum().item()), int(sg['active'].sum().item()),
+                                                                   floor, thr, n_windows, n_clips)
+                if not write:
+                    all_gate.append(sg['counts'][:n_clips])
             if retiming:
                 summary[name]['retime'] = model_retime_summary({'counts': rt['counts'].cpu().numpy(), 'nearest_src': nearest},
                                                                video['n_frames'], fps_pq[0], fps_pq[1], retime)
@@ -927,6 +1210,8 @@ def build_clips(root_dir, speaker, start_frame=80, num_frames=64, shoulder_chunk
         out['audio_lengths'] = torch.cat(all_len)
         if repair:
             out['repaired_per_clip'] = torch.cat(all_rep)
+        if gate is not None:
+            out['speech_counts'] = torch.cat(all_gate) if all_gate else torch.empty((0, 2), dtype=torch.int32, device=dev)
     assert isinstance(out['table'], pd.DataFrame)
     return out
 
@@ -949,6 +1234,53 @@ def add_retime_options(ap):
                     help='a retimed point is kept if the valid source points under its taps carry at least S of their weight (0 < S <= 1)')
 
 
+def add_speech_gate_options(ap):
+    d = GATE_DEFAULTS
+    ap.add_argument('--speech-gate', type=int, default=None, metavar='PERMILLE',
+                    help='keep a window only if at least PERMILLE (1..1000) thousandths of the 10 ms hops in its audio span lie above the '
+                         "track's noise floor (section 28; it measures audio energy, not speech: music passes; default: off)")
+    ap.add_argument('--gate-margin-db', type=float, default=d['margin_db'], metavar='DB', help='a hop is active this far above the floor (0..60)')
+    ap.add_argument('--gate-floor-pct', type=int, default=d['floor_pct'], metavar='PCT',
+                    help='the floor is the hop energy at this percentile of the track (0..50)')
+    ap.add_argument('--gate-abs-dbfs', type=float, default=d['abs_dbfs'], metavar='DBFS',
+                    help='no hop below this mean square level is active, whatever the floor (-120..0)')
+    ap.add_argument('--gate-hang-ms', type=int, default=10 * d['hang_hops'], metavar='MS',
+                    help='an inactive stretch of at most MS between active hops counts as active (a multiple of 10, at most 10240; 0: off)')
+    ap.add_argument('--gate-min-ms', type=int, default=10 * d['min_run_hops'], metavar='MS',
+                    help='an active stretch shorter than MS is dropped first (a multiple of 10, at most 10240; 0: off)')
+
+
+def speech_gate_option(a, default_permille=None):
+    """the parsed ``add_speech_gate_options`` arguments -> build_clips' ``speech_gate`` (without --speech-gate: None, or the --gate-*
+    values with ``default_permille`` where one is given)"""
+    if a.speech_gate is None and default_permille is None:
+        return None
+    return speech_gate_params({'min_permille': default_permille if a.speech_gate is None else a.speech_gate, 'margin_db': a.gate_margin_db, 'floor_pct': a.gate_floor_pct,
+                               'abs_dbfs': a.gate_abs_dbfs, 'hang_hops': gate_ms_to_hops(a.gate_hang_ms, '--gate-hang-ms'),
+                               'min_run_hops': gate_ms_to_hops(a.gate_min_ms, '--gate-min-ms')})
+
+
+def activity_report(wav, gate=None, device='cuda'):
+    """the hop statistics of one wav from its first sample on, without building anything -> the ``speech_gate`` summary (no windows)"""
+    import torch
+    params = speech_gate_params(gate if gate is not None else {'min_permille': 500})
+    sr_in, pcm = _read_wav(wav)
+    audio = device_resample(device_pcm_to_mono(pcm, 0, torch.device(device)), sr_in)
+    sg = device_speech_gate(audio, torch.empty(0, dtype=torch.int32, device=audio.device), [], params)
+    if int(sg['flag'].item()):
+        raise ValueError('%s: non-finite audio samples (a hop energy is not finite)' % wav)
+    n_hops = sg['energy'].numel()
+    floor, thr = (float(v) for v in sg['stats'].cpu().numpy()) if n_hops else (None, None)
+    return speech_gate_summary(n_hops, int(sg['active_raw'].sum().item()), int(sg['active'].sum().item()), floor, thr, 0, 0)
+
+
+def _gate_text(g):
+    if not g['hops']:
+        return 'no audio hop'
+    return '%d of %d hops active (%d before smoothing), floor %.1f dB, threshold %.1f dB%s' % (
+        g['active'], g['hops'], g['active_raw'], g['floor_db'], g['thr_db'], '' if g['note'] is None else '; NOTE: ' + g['note'])
+
+
 def despike_option(ap, values):
     if values is None:
         return None
@@ -960,18 +1292,30 @@ def despike_option(ap, values):
 def main(argv=None):
     ap = argparse.ArgumentParser(description="a speaker's clips on the GPU from per-frame keypoints and one wav per video (the reference's "
                                              "2_2, 2_3, 3_1 and 3_2) -> clips/npz, processed_137.csv, clips.csv")
-    ap.add_argument('--root', required=True, help='dataset root (DATASET.ROOT_DIR)')
-    ap.add_argument('--speaker', required=True)
+    ap.add_argument('--root', default=None, help='dataset root (DATASET.ROOT_DIR)')
+    ap.add_argument('--speaker', default=None)
     ap.add_argument('--start-frame', type=int, default=80, help="frames before it are dropped (3_1's -fi)")
     ap.add_argument('--frames', type=int, default=64, help='frames per clip (DATASET.NUM_FRAMES)')
     ap.add_argument('--shoulder-chunks', type=int, default=1, help="chunks of the shoulder-distance mean (2_3's -np)")
     ap.add_argument('--no-write', action='store_true', help='build on the device and print the summary only')
     add_repair_options(ap)
     add_retime_options(ap)
+    add_speech_gate_options(ap)
+    ap.add_argument('--activity-report', default=None, metavar='WAV',
+                    help="print the gate's hop statistics of one wav (with the --gate-* options) and build nothing")
     a = ap.parse_args(argv)
+    try:
+        gate = speech_gate_option(a, 500 if a.activity_report is not None else None)  # (the report counts no window: any share will do)
+    except ValueError as e:
+        ap.error(str(e))
+    if a.activity_report is not None:
+        print('%s: %s' % (a.activity_report, _gate_text(activity_report(a.activity_report, gate))))
+        return 0
+    if a.root is None or a.speaker is None:
+        ap.error('the following arguments are required: --root, --speaker')
     res = build_clips(a.root, a.speaker, start_frame=a.start_frame, num_frames=a.frames, shoulder_chunks=a.shoulder_chunks, write=not a.no_write,
                       repair_max_gap=a.repair_max_gap, despike=despike_option(ap, a.despike), source_fps=a.source_fps, retime=a.retime,
-                      retime_min_support=a.retime_min_support)
+                      retime_min_support=a.retime_min_support, speech_gate=gate)
     for name, s in res['videos'].items():
         k = s['timing']
         r = s.get('repair')
@@ -984,6 +1328,9 @@ def main(argv=None):
             fixed += ', source %s fps: %d -> %d frames (%s, %d of %d retimed points invalid)' % (
                 '%d/%d' % (t['P'], t['Q']) if t['Q'] != 1 else '%d' % t['P'], t['source_frames'], t['frames'], t['mode'],
                 t['points_invalid_out'], t['frames'] * KP)
+        g = s.get('speech_gate')
+        if g is not None:
+            fixed += ', speech gate: %s, %s' % (_gate_text(g), g['clips'])
         print('video %s: %d frames, %d kept, %d dropped (%d missing), %d shoulder frames dropped by chunking, scalar %.9g, clips %d train / '
               '%d idle / %d dev (%.2f s reading, kernels %.3f ms, %.2f s writing)%s'
               % (name, s['frames'], s['kept'], s['dropped'], s['missing'], s['shoulder_dropped'], s['scalar'], s['clips']['train'],

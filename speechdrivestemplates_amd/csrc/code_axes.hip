@@ -11,6 +11,7 @@
 //               comparing d2 first and n second; one partial per (query tile, row chunk), then a final kernel over the partials.
 // Everything is float64 on values converted exactly from fp32, every operation rounded on its own (exact_f64.h); no floating-point atomics.
 #include "jacobi.h"
+#include "radix_select.h"
 
 namespace {
 
@@ -61,15 +62,8 @@ __global__ void __launch_bounds__(kThreads) sdt_code_axes_project_kernel(const f
 constexpr int kHistPairs = 32;       // (axis, rank) histograms of one workgroup in LDS: 32 x 256 x 4 bytes
 constexpr int kSelMaxGridX = 512;
 
-// float64 bits -> uint64 with the same order (negative numbers: all bits flipped; others: the sign bit set); -0.0 sorts just below +0.0
-__device__ __forceinline__ unsigned long long order_key(double v) {
-    const unsigned long long b = (unsigned long long)__double_as_longlong(v);
-    return (b >> 63) ? ~b : (b | 0x8000000000000000ull);
-}
-__device__ __forceinline__ double order_value(unsigned long long key) {
-    const unsigned long long b = (key >> 63) ? (key & 0x7fffffffffffffffull) : ~key;
-    return __longlong_as_double((long long)b);
-}
+using sdt_select::order_key;  // (radix_select.h: the key, its inverse and the digit choice, shared with speech_gate.hip)
+using sdt_select::order_value;
 
 inline int sel_cols_per_group(int R) { return std::max(1, kHistPairs / R); }
 
@@ -126,15 +120,7 @@ __global__ void __launch_bounds__(kThreads) sdt_code_axes_select_step_kernel(int
     __syncthreads();
     if (t != 0) return;
     long long rem = remain[pair];
-    int digit = 255;  // (counts of a consistent state always reach the rank; 255 keeps a corrupted one inside the table)
-    for (int d = 0; d < 256; ++d) {
-        const long long cnt = (long long)s_cnt[d];
-        if (rem < cnt) {
-            digit = d;
-            break;
-        }
-        rem -= cnt;
-    }
+    const int digit = sdt_select::pick_digit(s_cnt, &rem);
     const unsigned long long p = prefix[pair] | ((unsigned long long)digit << (56 - 8 * pass));
     prefix[pair] = p;
     remain[pair] = rem;
