@@ -385,6 +385,37 @@ int sdt_reg_loss_fwd_f32(const float* pred, const float* gt, const float* score,
 int sdt_reg_loss_bwd_f32(const float* pred, const float* gt, const float* score, const float* chan_w, const float* gout_reg,
                          const float* gout_vel, const double* denom, int B, int T, int C, double lambda_reg, double lambda_vel,
                          float min_conf, float* dpred, void* stream);
+/*
+ * Limb-length and limb-direction loss on the skeleton (csrc/bone_loss.hip).  pred, gt: fp32 (B, T, 2, K), channel
+ * c = xy * K + k of a frame's C = 2 K;  mean, std: float64 (B, C);  score: fp32 (B, T, C) or NULL;  edges: int32 (E, 2);  edge_w: float64
+ * (E) or NULL (1);  root: int32 (K), the part root of each keypoint or -1 (a root is itself in no part).  K <= 256, E <= 512.
+ *   P[k] = double(pred[k]) * std[k] + mean[k];  X[k] = P[k] + (root[k] >= 0 ? P[root[k]] : 0);  Q, Y the same from gt
+ *   live(k) = score_x[k] > min_conf and score_y[k] > min_conf and (root[k] < 0 or the same for root[k])   (score NULL: 1; strict)
+ *   edge (a, b): vp = X[b] - X[a], vg = Y[b] - Y[a], lp = |vp|, lg = |vg|, m = live(a) and live(b), md = m and lp > 0 and lg > 0
+ *   losses[0] = lambda_len * sum(m  w |lp - lg| / max(lg, min_len)) / max(sum m , 1)
+ *   losses[1] = lambda_dir * sum(md w (1 - vp.vg / (lp lg)))        / max(sum md, 1)
+ * Everything in float64, one rounding to fp32; per-frame partial sums and integer counts combined by one block in a fixed order, no
+ * atomics: two calls give the same bits.  Dead edges are selected away: what sits under the mask (NaN included) reaches neither a loss nor
+ * a gradient.  An empty sum gives exactly 0.  Nothing is read on the host: forward leaves denom[0..1] on the device for backward.
+ *   psum: >= 2 B T doubles, pcnt: >= 2 B T int64 (workspaces, contents irrelevant);  losses: 2 floats;  denom: 2 doubles.
+ * Forward is two launches, backward one:
+ *   dX[b] += g_e, dX[a] -= g_e over the live edges incident to a keypoint, in ascending edge order, with
+ *   g_e = cl w sign(lp - lg) / max(lg, min_len) * vp / lp  (0 where lp = 0)  -  cd w (vg / (lp lg) - (vp.vg) vp / (lp^3 lg))  (md only),
+ *   cl = (gout_len / denom[0]) * lambda_len, cd = (gout_dir / denom[1]) * lambda_dir;
+ *   dpred[k] = (float)(std[k] * (dX[k] + sum of dX[j] over the children j of k in ascending order)).
+ * inc_ptr (K + 1) / inc_edge (2 E): the edges incident to each keypoint, entry = 2 * e + (1 if the keypoint is the edge's a end);
+ * child_ptr (K + 1) / child_idx: the children of each keypoint (root[j] == k), ascending.  gout_len / gout_dir: one device float each,
+ * NULL = that loss has no upstream gradient.
+ */
+int sdt_bone_loss_fwd_f32(const float* pred, const float* gt, const float* score, const double* mean, const double* std,
+                          const int32_t* edges, const double* edge_w, const int32_t* root, int B, int T, int K, int E, double lambda_len,
+                          double lambda_dir, float min_conf, double min_len, double* psum, int64_t* pcnt, float* losses, double* denom,
+                          void* stream);
+int sdt_bone_loss_bwd_f32(const float* pred, const float* gt, const float* score, const double* mean, const double* std,
+                          const int32_t* edges, const double* edge_w, const int32_t* root, const int32_t* inc_ptr, const int32_t* inc_edge,
+                          const int32_t* child_ptr, const int32_t* child_idx, const float* gout_len, const float* gout_dir,
+                          const double* denom, int B, int T, int K, int E, double lambda_len, double lambda_dir, float min_conf,
+                          double min_len, float* dpred, void* stream);
 /* LSGAN terms (voice2pose.py:171-189, nn.MSELoss against a constant): loss = lambda * mean((scores - target)^2);
  * dscores = gout * 2 * lambda / n * (scores - target). */
 int sdt_mse_const_fwd_f32(const float* scores, int64_t n, float target, float lambda, float* loss, void* stream);

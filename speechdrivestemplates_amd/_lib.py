@@ -87,6 +87,9 @@ SIGNATURES = {
     "sdt_l1_loss_bwd_f32": [_p, _p, _p, _i64, _f, _p, _p],
     "sdt_reg_loss_fwd_f32": [_p, _p, _p, _p, _i, _i, _i, C.c_double, C.c_double, _f, _p, _p, _p, _p, _p],
     "sdt_reg_loss_bwd_f32": [_p, _p, _p, _p, _p, _p, _p, _i, _i, _i, C.c_double, C.c_double, _f, _p, _p],
+    "sdt_bone_loss_fwd_f32": [_p, _p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, C.c_double, C.c_double, _f, C.c_double, _p, _p, _p, _p, _p],
+    "sdt_bone_loss_bwd_f32": [_p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, C.c_double, C.c_double, _f,
+                              C.c_double, _p, _p],
     "sdt_mse_const_fwd_f32": [_p, _i64, _f, _f, _p, _p],
     "sdt_mse_const_bwd_f32": [_p, _p, _i64, _f, _f, _p, _p],
     "sdt_code_kl_fwd_f32": [_p, _p, _i, _i, _i, _f, _p, _p, _p, _p],

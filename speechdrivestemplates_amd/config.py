@@ -22,6 +22,14 @@ _DEFAULTS = {
             # REG_PART_WEIGHTS: [body, face, hands], three floats >= 0 that multiply the terms of keypoints 0-8 / 9-78 / 79-120 (not the
             # divisors).  None = 1 everywhere.
             "LAMBDA_VEL": 0.0, "REG_MIN_CONFIDENCE": None, "REG_PART_WEIGHTS": None,
+            # extensions (losses on the limbs of the skeleton, ops.BoneLossFn / csrc/bone_loss.hip; off by default = the
+            # step as it was), on the de-normalised global keypoints, over the limbs the renderer draws (PoseTransforms.skeleton_edges):
+            # LAMBDA_BONE >= 0: weight of G_bone_loss, the mean of |predicted length - true length| / max(true length, BONE_MIN_LENGTH).
+            # LAMBDA_BONE_DIR >= 0: weight of G_bone_dir_loss, the mean of 1 - cos between the predicted and the true limb vector.
+            # BONE_MIN_LENGTH > 0: the floor (de-normalised pixels) of the divisor of the length term.
+            # REG_MIN_CONFIDENCE (a limb is live where both ends, and their part roots, are) and REG_PART_WEIGHTS (a limb takes the
+            # weight of its part) apply to both when they are set.
+            "LAMBDA_BONE": 0.0, "LAMBDA_BONE_DIR": 0.0, "BONE_MIN_LENGTH": 1.0,
             "CLIP_CODE": {"DIMENSION": None, "LR_SCALING": 1.0, "TRAIN": True, "FRAME_VARIANT": False,
                           "SAMPLE_FROM_NORMAL": False, "TEST_WITH_GT_CODE": False, "EXTERNAL_CODE": False,
                           "EXTERNAL_CODE_PTH": None},
@@ -247,6 +255,29 @@ def check_reg_loss(cfg):
     if vel == 0 and conf is None and parts is None:
         return None
     return float(vel), None if conf is None else float(conf), None if parts is None else tuple(float(w) for w in parts)
+
+
+def check_bone_loss(cfg):
+    """Validate VOICE2POSE.GENERATOR.LAMBDA_BONE / LAMBDA_BONE_DIR / BONE_MIN_LENGTH (and the two keys of ``check_reg_loss`` the limb losses
+    reuse).  Returns None when both lambdas are 0 (no limb loss: the step as it was), else
+    (lambda_bone, lambda_bone_dir, min_length, min_confidence or None, (body, face, hands) or None) as Python floats."""
+    g = cfg.VOICE2POSE.GENERATOR
+    bone, bdir, lmin = g.LAMBDA_BONE, g.LAMBDA_BONE_DIR, g.BONE_MIN_LENGTH
+    pre = "VOICE2POSE.GENERATOR."
+    if not _is_number(bone) or bone < 0:
+        raise ValueError(pre + "LAMBDA_BONE must be a number >= 0, got %r" % (bone,))
+    if not _is_number(bdir) or bdir < 0:
+        raise ValueError(pre + "LAMBDA_BONE_DIR must be a number >= 0, got %r" % (bdir,))
+    if not _is_number(lmin) or not lmin > 0:
+        raise ValueError(pre + "BONE_MIN_LENGTH must be a number > 0, got %r" % (lmin,))
+    if bone == 0 and bdir == 0:
+        return None
+    reg = check_reg_loss(cfg)
+    conf, parts = (None, None) if reg is None else reg[1:]
+    if cfg.DATASET.NUM_LANDMARKS != 121:
+        raise ValueError(pre + "LAMBDA_BONE / LAMBDA_BONE_DIR need the 121-keypoint skeleton, DATASET.NUM_LANDMARKS is %r"
+                         % (cfg.DATASET.NUM_LANDMARKS,))
+    return float(bone), float(bdir), float(lmin), conf, parts
 
 
 def check_clip_metrics(cfg):

@@ -120,6 +120,42 @@ class PoseTransforms:
         other 69 hang off in ``_part_index``, is a face keypoint), HANDS 79-120 (left 79-99, right 100-120)."""
         return [PoseTransforms.BODY] * 9 + [PoseTransforms.FACE] * 70 + [PoseTransforms.HANDS] * 42
 
+    # the nine chains of the 68-point face outline (first point, last point, closed): jaw, two brows, nose bridge, nostrils, two eyes,
+    # outer and inner lips -- consecutive points joined, a closed chain's last point joined back to its first
+    _FACE_CHAINS = ((0, 16, False), (17, 21, False), (22, 26, False), (27, 30, False), (31, 35, False),
+                    (36, 41, True), (42, 47, True), (48, 59, True), (60, 67, True))
+
+    @staticmethod
+    def skeleton_edges():
+        """The 108 limbs (a, b) of the 121-keypoint skeleton in the order the renderer draws them (csrc/render.hip, K = 121): 5 body edges
+        (neck-relative upper body: shoulders 1 / 4, elbows 2 / 5, wrists 3 / 6), 63 face edges (the 68-point chains, behind the 9 body
+        keypoints), 2 x 20 hand edges (left hand from 79, right hand from 100: per finger f the wrist point to 4 f + 1, then 4 f + s to
+        4 f + s + 1)."""
+        edges = [(1, 4), (1, 2), (2, 3), (4, 5), (5, 6)]
+        for first, last, closed in PoseTransforms._FACE_CHAINS:
+            edges += [(9 + k, 9 + k + 1) for k in range(first, last)]
+            if closed:
+                edges.append((9 + last, 9 + first))
+        for base in (79, 100):
+            for f in range(5):
+                for s in range(4):
+                    edges.append((base + (4 * f + s if s else 0), base + 4 * f + s + 1))
+        return edges
+
+    @staticmethod
+    def part_roots(hierarchical=True):
+        """The part root of each of the 121 keypoints, -1 for a keypoint in no part (all of them when the poses are not hierarchical):
+        ``_part_index`` as one list"""
+        root = [-1] * 121
+        if hierarchical:
+            for k in _HEAD_IDX:
+                root[k] = HEAD_ROOT
+            for k in range(79, 100):
+                root[k] = HAND_ROOT_L
+            for k in range(100, 121):
+                root[k] = HAND_ROOT_R
+        return root
+
     def parted_to_global(self, poses):
         """gesture_dataset.py:147-155, in place: head / hand keypoints += their part's root (the roots themselves are in no part)."""
         sel, root = self._part_index(poses.device)

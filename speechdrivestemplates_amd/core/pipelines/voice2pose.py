@@ -18,7 +18,7 @@ import torch
 from torch import nn
 
 from ... import dp, ops
-from ...config import check_augment, check_clip_metrics, check_reg_loss
+from ...config import check_augment, check_bone_loss, check_clip_metrics, check_reg_loss
 from ...mel import MelSpectrogram
 from ...optim import FlatAdam
 from ..datasets.gesture_dataset import PoseTransforms
@@ -33,6 +33,15 @@ class Voice2PoseModel(nn.Module):
         # LAMBDA_VEL / REG_MIN_CONFIDENCE / REG_PART_WEIGHTS, validated; None = all at their defaults: the plain L1 mean (ops.L1LossFn)
         self.reg_opts = check_reg_loss(cfg)
         self._chan_w = {}  # device -> per-channel part weights (2 * 121 floats, x then y), built once
+        # LAMBDA_BONE / LAMBDA_BONE_DIR / BONE_MIN_LENGTH, validated; None = both lambdas 0: no limb loss, nothing is built or launched
+        self.bone_opts = check_bone_loss(cfg)
+        self.bone_table = None
+        if self.bone_opts is not None:  # the renderer's 108 limbs, each with the weight of its part
+            edges, parts = PoseTransforms.skeleton_edges(), self.bone_opts[4]
+            table = PoseTransforms.part_table()
+            assert all(table[a] == table[b] for a, b in edges)
+            self.bone_table = ops.BoneTable(edges, PoseTransforms.part_roots(bool(cfg.DATASET.HIERARCHICAL_POSE)),
+                                            None if parts is None else [parts[table[a]] for a, _ in edges])
         # TRAIN.AUGMENT, validated; None = off: no Augmenter exists and the forward pass is the one it was
         self.aug_opts = check_augment(cfg)
         self._augmenters = {}  # device -> augment.Augmenter (tables and workspaces), built by the first training forward pass
@@ -182,6 +191,19 @@ class Voice2PoseModel(nn.Module):
             if lam_vel > 0:
                 losses['G_vel_loss'] = vel
                 g_loss = g_loss + vel
+        if self.bone_opts is not None:  # limb length / limb direction on the de-normalised global keypoints, one fused op (section 29)
+            lam_bone, lam_dir, min_len, min_conf, _ = self.bone_opts
+            stat = batch['speaker_stat']
+            score = batch['poses_score'].to(dev, non_blocking=True) if min_conf is not None else None
+            bone, bone_dir = ops.BoneLossFn.apply(poses_pred, poses_gt, stat['mean'].to(dev, non_blocking=True),
+                                                  stat['std'].to(dev, non_blocking=True), score, self.bone_table, lam_bone, lam_dir,
+                                                  min_conf, min_len)
+            if lam_bone > 0:
+                losses['G_bone_loss'] = bone
+                g_loss = g_loss + bone
+            if lam_dir > 0:
+                losses['G_bone_dir_loss'] = bone_dir
+                g_loss = g_loss + bone_dir
         if kl is not None:
             losses['G_clipcode_kl_loss'] = kl
             results['kl_valid'] = kl_valid

@@ -1861,6 +1861,112 @@ class RegLossFn(torch.autograd.Function):
         return (dp,) + (None,) * 6
 
 
+def bone_incidence(edges, K):
+    """CSR list of the edges incident to each of ``K`` keypoints: (inc_ptr[K + 1], inc_edge[2 E]), entry = 2 * e + (1 if the keypoint is
+    edge e's first end, where the edge's gradient enters with a minus sign), edges ascending within a keypoint"""
+    rows = [[] for _ in range(K)]
+    for e, (a, b) in enumerate(edges):
+        rows[a].append(2 * e + 1)
+        rows[b].append(2 * e)
+    ptr = [0]
+    for r in rows:
+        ptr.append(ptr[-1] + len(r))
+    return ptr, [x for r in rows for x in r]
+
+
+class BoneTable:
+    """The skeleton a BoneLossFn call runs on: edges (E, 2), the part root of each of K keypoints (-1: none) and one weight per edge (None:
+    1), validated ON THE HOST once -- K <= 256, E <= 512, indices inside [0, K), no edge from a keypoint to itself, a root that is itself in
+    no part, finite weights >= 0 -- with the incidence and children lists backward gathers through.  ``on(device)`` uploads the tables once
+    per device: no host-to-device copy inside a step, which a hipGraph capture would refuse."""
+    MAX_K, MAX_E = 256, 512
+
+    def __init__(self, edges, root, edge_w=None):
+        edges = [(int(a), int(b)) for a, b in edges]
+        root = [int(r) for r in root]
+        K, E = len(root), len(edges)
+        if not 0 < K <= self.MAX_K or E > self.MAX_E:
+            raise ValueError("BoneTable: 0 < K <= %d keypoints and E <= %d edges are supported, got K = %d, E = %d"
+                             % (self.MAX_K, self.MAX_E, K, E))
+        for e, (a, b) in enumerate(edges):
+            if not (0 <= a < K and 0 <= b < K) or a == b:
+                raise ValueError("BoneTable: edge %d = (%d, %d) must join two different keypoints of [0, %d)" % (e, a, b, K))
+        for k, r in enumerate(root):
+            if r < -1 or r >= K or r == k:
+                raise ValueError("BoneTable: root[%d] = %d must be -1 or another keypoint of [0, %d)" % (k, r, K))
+            if r >= 0 and root[r] >= 0:
+                raise ValueError("BoneTable: root[%d] = %d is itself in a part (root[%d] = %d): a root must be in no part" % (k, r, r, root[r]))
+        if edge_w is not None:
+            edge_w = [float(w) for w in edge_w]
+            if len(edge_w) != E or not all(w >= 0 and w != float('inf') for w in edge_w):
+                raise ValueError("BoneTable: edge_w must hold one finite weight >= 0 per edge, got %r" % (edge_w,))
+        self.K, self.E, self.edges, self.root, self.edge_w = K, E, edges, root, edge_w
+        self.inc_ptr, self.inc_edge = bone_incidence(edges, K)
+        kids = [[j for j in range(K) if root[j] == k] for k in range(K)]
+        self.child_ptr = [0]
+        for c in kids:
+            self.child_ptr.append(self.child_ptr[-1] + len(c))
+        self.child_idx = [j for c in kids for j in c]
+        self._dev = {}
+
+    def on(self, dev):
+        key = str(dev)
+        if key not in self._dev:
+            i32 = lambda v, shape=None: torch.tensor(v, dtype=torch.int32).reshape(shape or (len(v),)).to(dev)  # noqa: E731
+            self._dev[key] = (i32(self.edges, (self.E, 2)), None if self.edge_w is None else torch.tensor(self.edge_w, dtype=torch.float64).to(dev),
+                              i32(self.root), i32(self.inc_ptr), i32(self.inc_edge), i32(self.child_ptr), i32(self.child_idx))
+        return self._dev[key]
+
+
+class BoneLossFn(torch.autograd.Function):
+    """Relative limb-length error and 1 - cos of the limb direction between prediction and ground truth, on the de-normalised global
+    keypoints (csrc/bone_loss.hip): (bone, bone_dir) =
+    (lam_len * sum(m w |lp - lg| / max(lg, min_len)) / max(sum m, 1), lam_dir * sum(md w (1 - vp.vg / (lp lg))) / max(sum md, 1)) over the
+    edges of ``table`` (a BoneTable) in every frame of pred, gt (B, T, 2, K) fp32; mean, std: float64 (B, 2 K); score: (B, T, 2, K) or None.
+    Two launches forward, one backward; the divisors stay on the device."""
+
+    @staticmethod
+    def forward(ctx, pred, gt, mean, std, score, table, lam_len, lam_dir, min_conf, min_len):
+        _req_cuda(pred, gt, mean, std)
+        K, E = table.K, table.E
+        assert pred.dim() == 4 and pred.shape[2:] == (2, K) and pred.shape == gt.shape and pred.dtype == gt.dtype == torch.float32
+        pred, gt = pred.contiguous(), gt.contiguous()
+        B, T = pred.shape[0], pred.shape[1]
+        assert mean.shape == std.shape == (B, 2 * K) and mean.dtype == std.dtype == torch.float64
+        mean, std = mean.contiguous(), std.contiguous()
+        if score is not None:
+            _req_cuda(score)
+            assert score.shape == pred.shape and score.dtype == torch.float32 and min_conf is not None
+            score = score.contiguous()
+        dev = pred.device
+        tabs = table.on(dev)
+        psum = torch.empty(2 * B * T, device=dev, dtype=torch.float64)
+        pcnt = torch.empty(2 * B * T, device=dev, dtype=torch.int64)
+        losses = torch.empty(2, device=dev, dtype=torch.float32)
+        denom = torch.empty(2, device=dev, dtype=torch.float64)
+        ctx.args = (B, T, K, E, float(lam_len), float(lam_dir), 0.0 if score is None else float(min_conf), float(min_len))
+        edges, edge_w, root = tabs[:3]
+        check(_lib.load().sdt_bone_loss_fwd_f32(_p(pred), _p(gt), _p(score), _p(mean), _p(std), _p(edges), _p(edge_w), _p(root), *ctx.args,
+                                                _p(psum), _p(pcnt), _p(losses), _p(denom), _stream()))
+        ctx.save_for_backward(pred, gt, mean, std, score, denom)
+        ctx.tabs = tabs
+        ctx.set_materialize_grads(False)  # backward takes None for a loss that nothing consumed
+        bone, bone_dir = losses.unbind(0)
+        return bone, bone_dir
+
+    @staticmethod
+    def backward(ctx, g_len, g_dir):
+        pred, gt, mean, std, score, denom = ctx.saved_tensors
+        if g_len is None and g_dir is None:
+            return (None,) * 10
+        dp = torch.empty_like(pred)
+        g_len = None if g_len is None else g_len.contiguous()
+        g_dir = None if g_dir is None else g_dir.contiguous()
+        check(_lib.load().sdt_bone_loss_bwd_f32(_p(pred), _p(gt), _p(score), _p(mean), _p(std), *(_p(t) for t in ctx.tabs), _p(g_len),
+                                                _p(g_dir), _p(denom), *ctx.args, _p(dp), _stream()))
+        return (dp,) + (None,) * 9
+
+
 class MseConstFn(torch.autograd.Function):
     """lambda * mean((scores - target)^2): the LSGAN generator / discriminator terms (voice2pose.py:171-189)."""
 
