@@ -327,9 +327,20 @@ def run_case(ops, c, d, belows, expect, label):
     got = served(ops, c, dev)
     assert got == expect, "%s%s: served by %r, the table says %r" % (tag, label, got, expect)
     name = tag + label
-    xd, gyd = d.x.to(BF).to(DEV), d.gy.to(BF).to(DEV)
-    wd = torch.nn.Parameter(ops.to_weight_layout(d.w.float()).to(DEV))
     errs = {}
+    run_forward(ops, c, d, expect, name, errs)
+    run_backward(ops, c, d, belows, expect, name, errs, tag in ACCUMULATE)
+    assert not ops.streamk_error_codes(), name
+    print("  case %-22s fwd %-28s dX %-32s dW %-28s | %s" % (name, expect.fwd, expect.dx, expect.dw,
+                                                             "  ".join("%s %.2e" % kv for kv in errs.items())))
+
+
+def run_forward(ops, c, d, expect, name, errs):
+    """the forward half of a case: ConvStatsFn under every grouping for which a bf16 forward launch exists"""
+    tag = c[0]
+    B, Hi, Wi, Cin, Cout, kh, kw, s, p, Ho, Wo = dims(c)
+    xd = d.x.to(BF).to(DEV)
+    wd = torch.nn.Parameter(ops.to_weight_layout(d.w.float()).to(DEV))
 
     def note(key, e):
         errs[key] = max(errs.get(key, 0.0), e)
@@ -351,6 +362,21 @@ def run_case(ops, c, d, belows, expect, label):
                 key = "%s %s %s" % (tag, mode, q)
                 note(mode + " " + q, rel_err(sums[..., k], ref))
                 check("%s %s %s" % (name, mode, q), sums[..., k], ref, tol_for(key, TOL_SUMS))
+
+
+def run_backward(ops, c, d, belows, expect, name, errs, accumulate, tol_for=tol_for):
+    """the backward half of a case (callable alone: tests/test_reserved_conv_sweep_gpu.py runs it under a reserve, twice): dx under three
+    holders, the backward sums, dW; ``accumulate``: a second dW call and a call onto a pre-filled .grad as well.  Returns every tensor a launch
+    produced (dx and the statistics per holder, the first dW), for a caller that compares two runs bit for bit."""
+    tag = c[0]
+    B, Hi, Wi, Cin, Cout, kh, kw, s, p, Ho, Wo = dims(c)
+    xd, gyd = d.x.to(BF).to(DEV), d.gy.to(BF).to(DEV)
+    wd = torch.nn.Parameter(ops.to_weight_layout(d.w.float()).to(DEV))
+    outs = []
+
+    def note(key, e):
+        errs[key] = max(errs.get(key, 0.0), e)
+        return e
     # ---- input gradient: no holder, IN holder, BN holder
     dead = unreachable(c)
     for mode, groups in [(None, 0)] + holder_modes(c):
@@ -358,6 +384,7 @@ def run_case(ops, c, d, belows, expect, label):
         dxd = ops.conv_input_grad(gyd, wd, (B, Hi, Wi, Cin), s, p, h)
         torch.cuda.synchronize()
         what = "%s dx%s" % (name, "" if mode is None else " (%s holder)" % mode)
+        outs += [dxd] + ([] if h is None or h.sums is None else [h.sums])
         if expect.dx is None:  # refused: the fp32 kernels took it, and no statistics were accumulated from the bf16 y
             assert dxd.dtype == torch.float32 and (h is None or h.sums is None)
             note("dx (fp32)", rel_err(dxd, d.dx))
@@ -382,7 +409,8 @@ def run_case(ops, c, d, belows, expect, label):
     torch.cuda.synchronize()
     note("dW", rel_err(wd.grad, d.dw))
     check(name + " dW", wd.grad, d.dw, tol_dw)
-    if tag in ACCUMULATE:
+    outs.append(wd.grad.clone())
+    if accumulate:
         assert expect.dw is not None
         ops.conv_weight_grad(xd, gyd, wd, s, p)
         check(name + " dW, second call adds", wd.grad, 2.0 * d.dw, tol_dw)
@@ -392,9 +420,7 @@ def run_case(ops, c, d, belows, expect, label):
         ops.conv_weight_grad(xd, gyd, wd, s, p)
         torch.cuda.synchronize()
         check(name + " dW onto a pre-filled .grad", wd.grad, fill.float().double() + d.dw, tol_dw)
-    assert not ops.streamk_error_codes(), name
-    print("  case %-22s fwd %-28s dX %-32s dW %-28s | %s" % (name, expect.fwd, expect.dx, expect.dw,
-                                                             "  ".join("%s %.2e" % kv for kv in errs.items())))
+    return outs
 
 
 @pytest.mark.gpu

@@ -513,17 +513,31 @@ def _param(ops, w):
 
 def run_case(ops, c, d, belows, expect, label, split):
     tag = c[0]
-    B, Hi, Wi, Cin, Cout, kh, kw, s, p, Ho, Wo = dims(c)
     dev = torch.device(DEV, torch.cuda.current_device())
     got = served(ops, c, dev)
     assert got == expect, "%s%s: served by %r, the table says %r" % (tag, label, got, expect)
     name = tag + label
-    xd, gyd = d.x.float().to(DEV), d.gy.float().to(DEV)
-    wd = _param(ops, d.w)
     errs = {}
+    run_forward(ops, c, d, name, errs)
+    run_backward(ops, c, d, belows, expect, name, errs, (tag, split) in ACCUMULATE)
+    assert not ops.streamk_error_codes(), name
+    print("  case %-24s fwd %-36s dX %-52s dW %-30s %-28s | %s" % (name, expect.fwd, expect.dx, expect.dw, expect.stats,
+                                                                   "  ".join("%s %.2e" % kv for kv in errs.items())))
+
+
+def _note(errs, key, e):
+    errs[key] = max(errs.get(key, 0.0), e)
+
+
+def run_forward(ops, c, d, name, errs, tol=None):
+    """the forward half of a case: y without and with a bias, ConvStatsFn under every grouping conv_stats_fusable accepts"""
+    tag, tol = c[0], tol or tol_for  # (tol: another module's table of measured fp32 reference errors)
+    B, Hi, Wi, Cin, Cout, kh, kw, s, p, Ho, Wo = dims(c)
+    xd = d.x.float().to(DEV)
+    wd = _param(ops, d.w)
 
     def note(key, e):
-        errs[key] = max(errs.get(key, 0.0), e)
+        _note(errs, key, e)
 
     # ---- forward without and with a bias, twice
     bias = bias_of(c)
@@ -535,8 +549,8 @@ def run_case(ops, c, d, belows, expect, label, split):
     yb = ops.conv_forward(xd, wd, bias.float().to(DEV), s, p)
     torch.cuda.synchronize()
     note("y", rel_err(y0, d.y))
-    check(name + " y", y0, d.y, tol_for(tag + " y", TOL_Y))
-    check(name + " y+bias", yb, d.y + bias, tol_for(tag + " y+bias", TOL_Y))
+    check(name + " y", y0, d.y, tol(tag + " y", TOL_Y))
+    check(name + " y+bias", yb, d.y + bias, tol(tag + " y+bias", TOL_Y))
     assert torch.equal(y0, y1), "%s: the second forward run differs from the first" % name
     # ---- forward with the statistics epilogue, under each grouping for which conv_stats_fusable says yes
     for mode, groups in modes(c):
@@ -552,12 +566,26 @@ def run_case(ops, c, d, belows, expect, label, split):
         torch.cuda.synchronize()
         (ys, sums), (ys1, sums1) = runs
         note("y", rel_err(ys, d.y))
-        check("%s y (%s statistics)" % (name, mode), ys, d.y, tol_for(tag + " y", TOL_Y))
+        check("%s y (%s statistics)" % (name, mode), ys, d.y, tol(tag + " y", TOL_Y))
         assert torch.equal(ys, ys1) and torch.equal(sums, sums1), "%s: the second %s statistics run differs from the first" % (name, mode)
         sums = sums.view(groups, Cout, 2)
         for k, (q, ref) in enumerate(zip(("sum", "sumsq"), fwd_sums(d.y, groups))):
             note(mode + " " + q, rel_err(sums[..., k], ref))
-            check("%s %s %s" % (name, mode, q), sums[..., k], ref, tol_for("%s %s %s" % (tag, mode, q), TOL_SUMS))
+            check("%s %s %s" % (name, mode, q), sums[..., k], ref, tol("%s %s %s" % (tag, mode, q), TOL_SUMS))
+
+
+def run_backward(ops, c, d, belows, expect, name, errs, accumulate, tol=None):
+    """the backward half of a case (callable alone: tests/test_reserved_conv_sweep_gpu.py runs it under a reserve): dx under three holders, the
+    backward sums where ``expect.stats`` says they fuse, dW; ``accumulate``: a second dW call and a call onto a pre-filled .grad as well"""
+    tag, tol = c[0], tol or tol_for  # (tol: another module's table of measured fp32 reference errors)
+    B, Hi, Wi, Cin, Cout, kh, kw, s, p, Ho, Wo = dims(c)
+    dev = torch.device(DEV, torch.cuda.current_device())
+    xd, gyd = d.x.float().to(DEV), d.gy.float().to(DEV)
+    wd = _param(ops, d.w)
+
+    def note(key, e):
+        _note(errs, key, e)
+
     # ---- input gradient: no holder, IN holder, BN holder; twice each
     dead = unreachable(c)
     for mode, groups in [(None, 0)] + holder_modes(c):  # (one row per group: every pre-activation sits ON the kink -- no holder there)
@@ -570,7 +598,7 @@ def run_case(ops, c, d, belows, expect, label, split):
         (dxd, h), (dxd1, h1) = runs
         what = "%s dx%s" % (name, "" if mode is None else " (%s holder)" % mode)
         note("dx", rel_err(dxd, d.dx))
-        check(what, dxd, d.dx, tol_for(tag + " dx", TOL_DX))
+        check(what, dxd, d.dx, tol(tag + " dx", TOL_DX))
         assert torch.equal(dxd, dxd1), "%s: the second run differs from the first" % what
         if bool(dead.any()):
             z = dxd[:, dead.to(DEV)]
@@ -584,9 +612,9 @@ def run_case(ops, c, d, belows, expect, label, split):
                 bs = h.sums.view(groups, Cin, 2)
                 for k, (q, ref) in enumerate(zip(("sum g", "sum g yhat"), bwd_sums(belows[mode], d.dx))):
                     note("%s %s" % (mode, q), rel_err(bs[..., k], ref))
-                    check("%s %s bwd %s" % (name, mode, q), bs[..., k], ref, tol_for("%s %s bwd %s" % (tag, mode, q), TOL_BSUMS))
+                    check("%s %s bwd %s" % (name, mode, q), bs[..., k], ref, tol("%s %s bwd %s" % (tag, mode, q), TOL_BSUMS))
     # ---- weight gradient into a fresh .grad, twice; for one case per kernel also a second call and a call onto a pre-filled .grad
-    tol_dw = tol_for(tag + " dW", TOL_DW)
+    tol_dw = tol(tag + " dW", TOL_DW)
     ops.conv_weight_grad(xd, gyd, wd, s, p)
     wd1 = _param(ops, d.w)
     ops.conv_weight_grad(xd, gyd, wd1, s, p)
@@ -594,7 +622,7 @@ def run_case(ops, c, d, belows, expect, label, split):
     note("dW", rel_err(wd.grad, d.dw))
     check(name + " dW", wd.grad, d.dw, tol_dw)
     assert torch.equal(wd.grad, wd1.grad), "%s: the second dW run differs from the first" % name
-    if (tag, split) in ACCUMULATE:
+    if accumulate:
         ops.conv_weight_grad(xd, gyd, wd, s, p)
         check(name + " dW, second call adds", wd.grad, 2.0 * d.dw, tol_dw)
         fill = (((torch.arange(d.dw.numel(), dtype=torch.float64) * 7919) % 13 - 6.0) * 0.125 * float(d.dw.abs().max())).reshape(d.dw.shape)
@@ -603,9 +631,6 @@ def run_case(ops, c, d, belows, expect, label, split):
         ops.conv_weight_grad(xd, gyd, wd, s, p)
         torch.cuda.synchronize()
         check(name + " dW onto a pre-filled .grad", wd.grad, fill.float().double() + d.dw, tol_dw)
-    assert not ops.streamk_error_codes(), name
-    print("  case %-24s fwd %-36s dX %-52s dW %-30s %-28s | %s" % (name, expect.fwd, expect.dx, expect.dw, expect.stats,
-                                                                   "  ".join("%s %.2e" % kv for kv in errs.items())))
 
 
 @pytest.mark.gpu
