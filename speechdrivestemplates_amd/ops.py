@@ -893,12 +893,18 @@ class WeightMirrors:
             return None
         ptr = operand.data_ptr()
         hit, which = WeightMirrors._by_ptr.get(ptr), 3
+        if hit is not None and hit[0]() is None:
+            # a dead group's WEIGHT lived at this address: the allocator may have handed the block to a live group's mirror, whose planes
+            # the stale key would hide (the launch then split in its loader: same bits, but the pre-split operand was silently not used)
+            del WeightMirrors._by_ptr[ptr]
+            hit = None
         if hit is None:
             hit, which = WeightMirrors._by_mirror.get(ptr), 4
         if hit is None:
             return None
         owner = hit[0]()
         if owner is None:
+            WeightMirrors._by_mirror.pop(ptr, None)
             return None
         e = owner.entries[hit[1]]
         if e[0].dim() != 4 or (e[0].data_ptr() if which == 3 else e[1].data_ptr()) != ptr:
