@@ -34,6 +34,8 @@ import math
 
 import numpy as np
 
+from ._exact_model import _butterfly_wave
+
 REC_COLS = 32  # words of a clip's record (SDT_AUGMENT_REC_COLS)
 IG, IS, SHIFT, POLARITY, NOISE_ON, SIGMA, SS, NONFINITE, FREQ0, TIME0, NF, NT = 0, 1, 2, 3, 4, 5, 6, 7, 8, 16, 24, 25
 CHUNK, LANES, MAX_MASKS, MAX_L, MAX_B = 1024, 64, 4, 1 << 24, 65535
@@ -105,14 +107,6 @@ def noise_prob24(opts):
     return 0 if opts['snr'] is None else int(math.floor(float(opts['noise_prob']) * (1 << 24)))
 
 
-def _butterfly(v):
-    """the xor butterfly 32, 16, 8, 4, 2, 1 along the last axis of 64 lanes -> lane 0's value (every lane holds the same bits)"""
-    idx = np.arange(LANES)
-    for o in (32, 16, 8, 4, 2, 1):
-        v = v + v[..., idx ^ o]
-    return v[..., 0]
-
-
 def sumsq_model(x):
     """(B, L) float32 -> (B,) float64: the sum of squares in the order of sdt_augment_sumsq_f64"""
     x = np.asarray(x, dtype=np.float32)
@@ -125,7 +119,7 @@ def sumsq_model(x):
         s = np.zeros((B, n_chunks, 256))
         for k in range(4):
             s = s + sq[:, :, k]
-        waves = _butterfly(s.reshape(B, n_chunks, 4, LANES))
+        waves = _butterfly_wave(s.reshape(B, n_chunks, 4, LANES))
         partials = ((waves[..., 0] + waves[..., 1]) + waves[..., 2]) + waves[..., 3]
         rounds = -(-n_chunks // LANES)
         p = np.zeros((B, rounds * LANES))
@@ -134,7 +128,7 @@ def sumsq_model(x):
         s = np.zeros((B, LANES))
         for j in range(rounds):
             s = s + p[:, j]
-        return _butterfly(s)
+        return _butterfly_wave(s)
 
 
 def clip_params_model(opts, clip, step, ss=0.0, L=1, words=None):

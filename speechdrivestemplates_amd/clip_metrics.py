@@ -23,16 +23,22 @@ Nothing is copied to the host before ``result()``.  There is no CPU fallback.
 reads ``poses_pred_batch`` / ``poses_gt_batch`` from the results/*.npz files of TEST.SAVE_NPZ (clips are numbered in file order), runs the
 device route and prints the epoch values and the N clips with the largest hand error.
 """
+from functools import partial
+
 import numpy as np
 
+from . import _record_table
+from ._exact_model import LANES, MAX_TABLES  # noqa: F401  (public names of this module)
+from ._exact_model import MAX_COPIES, MAX_K, PARTS, _norm2, _ordered_sum, _part_sums, _quotient, check_parts, part_sizes
+from ._record_table import CHUNK  # noqa: F401
+from ._record_table import RecordTable, check_num_clips, chunked_records
+
 COLS = 40  # words of a record (SDT_CLIP_METRICS_COLS)
-PARTS = ('all', 'body', 'face', 'hands')
 FLOAT_GROUPS = ('l2_sum', 'speed_pred', 'speed_gt', 'vel_l2', 'div_sum')  # words [0, 20): group g, part p at 4 g + p
 HIT0, SEEN, COPIES, NONFINITE, FRAMES = 20, 36, 37, 38, 39  # int64 words: pck_hit[a][p] at 20 + 4 a + p
 COLUMN_NAMES = tuple('%s_%s' % (g, p) for g in FLOAT_GROUPS for p in PARTS) + tuple('pck_hit_%d_%s' % (a, p) for a in range(4) for p in PARTS) + (
     'seen', 'copies', 'nonfinite', 'frames')
-MAX_K, MAX_ALPHAS, MAX_COPIES, MAX_TABLES, CHUNK = 128, 4, 16, 64, 64
-LANES = 128
+MAX_ALPHAS = 4
 # words of the epoch vector (include/sdt_hip.h): float64 [0, 36) in groups of 4 parts, then four int64
 OUT_L2, OUT_PCK, OUT_PCK_MEAN, OUT_SPEED_RATIO, OUT_VEL, OUT_DIV = 0, 4, 20, 24, 28, 32
 OUT_SEEN, OUT_NONFINITE, OUT_INDEX_ERRORS, OUT_PAIR_FRAMES = 36, 37, 38, 39
@@ -49,60 +55,11 @@ def check_alphas(alphas):
     return tuple(float(a) for a in alphas)
 
 
-def check_parts(parts, K):
-    """-> (K,) uint8 array; the default for K = 121 is PoseTransforms.part_table()"""
-    if parts is None:
-        if K != 121:
-            raise ValueError('a part table is needed for K = %d keypoints (the default is the 121-keypoint layout)' % K)
-        from .core.datasets.gesture_dataset import PoseTransforms
-        parts = PoseTransforms.part_table()
-    parts = np.asarray(parts)
-    if parts.shape != (K,) or not np.isin(parts, (0, 1, 2)).all():
-        raise ValueError('the part table must hold K = %d values in {0, 1, 2}' % K)
-    return parts.astype(np.uint8)
-
-
-def part_sizes(parts):
-    """(K, body, face, hands) keypoint counts"""
-    parts = np.asarray(parts)
-    return (int(parts.size),) + tuple(int((parts == p).sum()) for p in range(3))
-
-
 def alpha_name(a):
     return 'PCK_%g' % a
 
 
 # ---- the numpy contract model ------------------------------------------------------------------------------------------------------------------
-def _butterfly(v):
-    """(..., 128) lane values -> what every lane of the kernel ends with: the xor butterfly 32 .. 1 inside each 64-lane wave, wave 0 + wave 1"""
-    idx = np.arange(LANES)
-    for o in (32, 16, 8, 4, 2, 1):
-        v = v + v[..., idx ^ o]
-    return v[..., 0] + v[..., 64]
-
-
-def _part_sums(term, parts):
-    """(..., K) per-keypoint terms -> (..., 4): per part the lanes' values (+0.0 outside the part and for k >= K) through the butterfly"""
-    K = term.shape[-1]
-    lanes = np.zeros(term.shape[:-1] + (4, LANES))
-    for p in range(4):
-        lanes[..., p, :K] = term if p == 0 else np.where(parts == p - 1, term, 0.0)
-    return _butterfly(lanes)
-
-
-def _norm2(x, y):
-    return x * x + y * y  # (numpy rounds each operation on its own)
-
-
-def _ordered_sum(x, axis):
-    """serial sum along ``axis`` starting from +0.0"""
-    x = np.moveaxis(x, axis, 0)
-    s = np.zeros(x.shape[1:])
-    for i in range(x.shape[0]):
-        s = s + x[i]
-    return s
-
-
 def row_records_model(pred, gt, parts, alphas):
     """the (R, 40) int64 records of sdt_clip_metrics_rows_f64 (float64 words viewed as int64)"""
     pred, gt = np.asarray(pred, dtype=np.float64), np.asarray(gt, dtype=np.float64)
@@ -170,22 +127,13 @@ def unpack(records):
     return out
 
 
-def _quotient(x, n):
-    return np.float64(0.0) if n == 0 else np.float64(x) / np.float64(n)
-
-
 def epoch_model(tables, sizes, num_alphas, index_errors=0):
     """the 40 words of sdt_clip_metrics_epoch over ``tables``, a list of (N, 40) int64 record arrays, one per rank; ``sizes``: part_sizes()"""
-    tables = [np.asarray(t, dtype=np.int64) for t in tables]
-    N = tables[0].shape[0]
     tot_f, tot_i = np.zeros(20), np.zeros(48, dtype=np.int64)
     with np.errstate(all='ignore'):
-        for n0 in range(0, N, CHUNK):
+        for chunk in chunked_records(tables, SEEN):
             f, h = np.zeros(20), np.zeros(48, dtype=np.int64)
-            for n in range(n0, min(N, n0 + CHUNK)):
-                rec = next((t[n] for t in tables if t[n, SEEN] != 0), None)
-                if rec is None:
-                    continue
+            for rec in chunk:
                 h[SEEN] += 1
                 if rec[NONFINITE] != 0:
                     h[NONFINITE] += 1
@@ -235,35 +183,32 @@ BOOKKEEPING = ('clips_seen', 'index_errors')  # entries of result() that are not
 
 
 # ---- the device route (csrc/clip_metrics.hip) -------------------------------------------------------------------------------------------------
-class ClipMetricsAccumulator:
+class ClipMetricsAccumulator(RecordTable):
     """A table of ``num_clips`` clip records on ``device`` and its epoch values.
 
     ``add`` enqueues three launches (four with copies) on the current stream: no host synchronisation, and no allocation once the workspace has
     the step's shape (inputs that are not contiguous are made so, which allocates).  ``result`` is the only call that waits for the device.
-    The state is one (num_clips + 1, 40) int64 tensor: the records, then a header row whose word 0 counts the clip indices outside the table."""
+    The state is one (num_clips + 1, 40) int64 tensor: the records, then a header row whose word 0 counts the clip indices outside the table
+    (``RecordTable`` owns it, ``state``, ``table``, ``reset``, ``result`` and ``result_words``)."""
 
     def __init__(self, num_clips, K, alphas, device='cuda', parts=None):
         import ctypes as C
         import torch
         from . import _lib
-        num_clips, K = int(num_clips), int(K)
-        if num_clips < 1:
-            raise ValueError('the table needs at least one clip, got %d' % num_clips)
+        num_clips, K = check_num_clips(num_clips), int(K)
         if not 1 <= K <= MAX_K:
             raise ValueError('K = %d keypoints outside [1, %d]' % (K, MAX_K))
         self.alphas, self.parts = check_alphas(list(alphas)), check_parts(parts, K)
-        self.num_clips, self.K, self.device = num_clips, K, torch.device(device)
+        self.K, self.device = K, torch.device(device)
         if self.device.type != 'cuda':
             raise RuntimeError(_NO_GPU)
         if self.device.index is None:
             self.device = torch.device('cuda', torch.cuda.current_device())
         self._lib, self._C, self._torch = _lib.load(), C, torch
-        self._state = torch.zeros((num_clips + 1, COLS), dtype=torch.int64, device=self.device)
+        RecordTable.__init__(self, num_clips, self.device, COLS, 48, COLS)
         self._parts_dev = torch.from_numpy(self.parts).to(self.device)
         self._alphas_c = (C.c_double * len(self.alphas))(*self.alphas)
         self._sizes_c = (C.c_int64 * 4)(*part_sizes(self.parts))
-        self._epoch_work = torch.empty((-(-num_clips // CHUNK), 48), dtype=torch.int64, device=self.device)
-        self._out = torch.empty(COLS, dtype=torch.int64, device=self.device)
         self._work_shape, self._work = None, None
 
     def _stream(self):
@@ -327,42 +272,12 @@ class ClipMetricsAccumulator:
             _lib.check(self._lib.sdt_clip_metrics_commit(self._p(rows), self._p(div), self._p(idx), B, m, T, self._p(self._state),
                                                          self.num_clips, s))
 
-    def state(self):
-        """the (num_clips + 1, 40) int64 tensor (records, then the header row), for a collective"""
-        return self._state
+    def _launch_epoch(self, ptrs, ranks, stream):
+        return self._lib.sdt_clip_metrics_epoch(ptrs, ranks, self.num_clips, self._sizes_c, len(self.alphas), self._p(self._epoch_work),
+                                                self._p(self._out), stream)
 
-    def table(self):
-        """the (num_clips, 40) records, a view of the state"""
-        return self._state[:self.num_clips]
-
-    def reset(self):
-        self._state.zero_()
-
-    def result(self, gathered=None):
-        """-> the named epoch values (``epoch_values``) over this accumulator's table, or over ``gathered``: a (ranks, num_clips + 1, 40) int64
-        tensor (or a list of such states / accumulators), one entry per rank; the lowest rank that has seen a clip gives its record"""
-        return epoch_values(self.result_words(gathered), self.alphas)
-
-    def result_words(self, gathered=None):
-        """the 40 words of the epoch vector as a numpy int64 array (float64 words viewed as int64)"""
-        from . import _lib
-        torch, C = self._torch, self._C
-        if gathered is None:
-            blocks = [self._state]
-        elif torch.is_tensor(gathered):
-            blocks = list(gathered.unbind(0)) if gathered.ndim == 3 else [gathered]
-        else:
-            blocks = [g.state() if isinstance(g, ClipMetricsAccumulator) else g for g in gathered]
-        if not 1 <= len(blocks) <= MAX_TABLES:
-            raise ValueError('%d tables; the epoch stage takes 1 to %d' % (len(blocks), MAX_TABLES))
-        for b in blocks:
-            if b.dtype != torch.int64 or tuple(b.shape) != tuple(self._state.shape) or b.device != self.device or not b.is_contiguous():
-                raise ValueError('a gathered state must be a contiguous %s int64 tensor on %s' % (tuple(self._state.shape), self.device))
-        ptrs = (C.c_void_p * len(blocks))(*[b.data_ptr() for b in blocks])
-        with torch.cuda.device(self.device):
-            _lib.check(self._lib.sdt_clip_metrics_epoch(ptrs, len(blocks), self.num_clips, self._sizes_c, len(self.alphas),
-                                                        self._p(self._epoch_work), self._p(self._out), self._stream()))
-            return self._out.cpu().numpy()  # (same stream: ordered after the kernels, and the one wait of this class)
+    def epoch_values(self, words):
+        return epoch_values(words, self.alphas)
 
 
 def device_sqrt(x):
@@ -418,14 +333,7 @@ def hand_errors(records, sizes):
         return np.where((u['seen'] != 0) & (n > 0), u['l2_sum'][:, 3] / n, np.nan)
 
 
-def merge_tables(tables):
-    """(N, 40) record arrays, one per rank -> the records the epoch stage reads: per clip the lowest rank that has seen it"""
-    tables = [np.asarray(t, dtype=np.int64) for t in tables]
-    out = np.zeros_like(tables[0])
-    for t in tables:
-        take = (out[:, SEEN] == 0) & (t[:, SEEN] != 0)
-        out[take] = t[take]
-    return out
+merge_tables = partial(_record_table.merge_tables, seen=SEEN)  # (tables) -> per clip the record of the lowest rank that has seen it
 
 
 def save_table(path, records, alphas):

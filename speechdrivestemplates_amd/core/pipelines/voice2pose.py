@@ -551,8 +551,13 @@ class Voice2Pose(Trainer):
         """PCK, part errors, speed ratio, velocity error and diversity over the clips every rank delivered: the ranks' tables are all-gathered
         and clip by clip the lowest rank that has a record gives it, so every rank reports the same bits.  A clip with a non-finite sum is
         left out, counted and warned about; so is a clip index outside the table."""
-        from ...clip_metrics import BOOKKEEPING, merge_tables, save_table
-        acc = self.clip_metrics()
+        from ... import clip_metrics
+        return self._evaluate_record_table(self.clip_metrics(), clip_metrics, 'clip', '', epoch, tag, lambda acc: (acc.alphas,))
+
+    def _evaluate_record_table(self, acc, module, label, prefix, epoch, tag, save_args):
+        """the epoch values of one record table (``module``: clip_metrics or sync_metrics): all-gather the ranks' states, ``result``, warn
+        about clips left out, save the merged table with TEST.SAVE_NPZ (``save_args(acc)``: what ``module.save_table`` takes after the
+        records) and drop the bookkeeping entries"""
         if acc is None:  # no validation step ran
             return {}
         gathered = None
@@ -560,15 +565,16 @@ class Voice2Pose(Trainer):
             gathered = [torch.empty_like(acc.state()) for _ in range(torch.distributed.get_world_size())]
             torch.distributed.all_gather(gathered, acc.state())  # (the list form: nccl and gloo both have it)
         res = acc.result(gathered)
-        if res['clips_nonfinite'] or res['index_errors']:
-            logging.warning('[VAL] clip metrics: %d clip(s) left out for a non-finite sum, %d clip index(es) outside the table of %d'
-                            % (res['clips_nonfinite'], res['index_errors'], acc.num_clips))
+        if res[prefix + 'clips_nonfinite'] or res[prefix + 'index_errors']:
+            logging.warning('[VAL] %s metrics: %d clip(s) left out for a non-finite sum, %d clip index(es) outside the table of %d'
+                            % (label, res[prefix + 'clips_nonfinite'], res[prefix + 'index_errors'], acc.num_clips))
         if self.is_master_process() and self.cfg.TEST.SAVE_NPZ and self.base_path is not None:
             d = os.path.join(self.base_path, 'results')
             os.makedirs(d, exist_ok=True)
             tables = [acc.table()] if gathered is None else [g[:acc.num_clips] for g in gathered]
-            save_table('%s/epoch%d-%s-clip_metrics.npz' % (d, epoch, tag), merge_tables([t.cpu().numpy() for t in tables]), acc.alphas)
-        return {k: v for k, v in res.items() if k not in BOOKKEEPING}
+            module.save_table('%s/epoch%d-%s-%s_metrics.npz' % (d, epoch, tag, label), module.merge_tables([t.cpu().numpy() for t in tables]),
+                              *save_args(acc))
+        return {k: v for k, v in res.items() if k not in module.BOOKKEEPING}
 
     def uses_sync_metrics(self):
         return bool(getattr(self.cfg.TEST, 'SYNC_METRICS', False))
@@ -588,24 +594,8 @@ class Voice2Pose(Trainer):
     def evaluate_sync_metrics(self, epoch, tag):
         """precision, recall, offset and alignment of the beats against the audio onsets over the clips every rank delivered, merged as
         ``evaluate_clip_metrics`` merges its tables.  A clip with a non-finite sum is left out, counted and warned about."""
-        from ...sync_metrics import BOOKKEEPING, merge_tables, save_table
-        acc = self.sync_metrics()
-        if acc is None:  # no validation step ran
-            return {}
-        gathered = None
-        if self.cfg.SYS.DISTRIBUTED:
-            gathered = [torch.empty_like(acc.state()) for _ in range(torch.distributed.get_world_size())]
-            torch.distributed.all_gather(gathered, acc.state())  # (the list form: nccl and gloo both have it)
-        res = acc.result(gathered)
-        if res['sync_clips_nonfinite'] or res['sync_index_errors']:
-            logging.warning('[VAL] sync metrics: %d clip(s) left out for a non-finite sum, %d clip index(es) outside the table of %d'
-                            % (res['sync_clips_nonfinite'], res['sync_index_errors'], acc.num_clips))
-        if self.is_master_process() and self.cfg.TEST.SAVE_NPZ and self.base_path is not None:
-            d = os.path.join(self.base_path, 'results')
-            os.makedirs(d, exist_ok=True)
-            tables = [acc.table()] if gathered is None else [g[:acc.num_clips] for g in gathered]
-            save_table('%s/epoch%d-%s-sync_metrics.npz' % (d, epoch, tag), merge_tables([t.cpu().numpy() for t in tables]), acc.tol, acc.sigma)
-        return {k: v for k, v in res.items() if k not in BOOKKEEPING}
+        from ... import sync_metrics
+        return self._evaluate_record_table(self.sync_metrics(), sync_metrics, 'sync', 'sync_', epoch, tag, lambda acc: (acc.tol, acc.sigma))
 
     def evaluate_epoch(self, results_dict):
         from ...fgd import compute_fgd

@@ -10,11 +10,9 @@
 //                    o = 32, 16, 8, 4, 2, 1; then ((wave 0 + wave 1) + wave 2) + wave 3 is the chunk's partial;
 //   over the chunks  lane l of one wave adds the partials l, l + 64, l + 128, .. in that order from +0.0, then the same butterfly.
 // Every float64 multiply, add and divide goes through sdt_exact::*_rn (no FMA); every square is exact in float64.  No atomics.
-#include "exact_f64.h"
+#include "exact_lanes.h"
 
-using sdt_exact::add_rn;
-using sdt_exact::div_rn;
-using sdt_exact::mul_rn;
+using namespace sdt_exact;
 
 namespace {
 
@@ -47,13 +45,6 @@ __device__ __forceinline__ Words philox4x32(uint32_t c0, uint32_t c1, uint32_t c
     }
     return {{c0, c1, c2, c3}};
 }
-
-__device__ __forceinline__ double butterfly_sum(double v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = add_rn(v, __shfl_xor(v, o, 64));
-    return v;
-}
-__device__ __forceinline__ bool finite_d(double v) { return fabs(v) < __builtin_huge_val(); }  // false for NaN and +-inf
 
 // one workgroup of 256 threads per (chunk, clip): the chunk's partial sum of squares
 __global__ __launch_bounds__(256) void aug_sumsq_chunk_kernel(const float* __restrict__ x, int L, int n_chunks, double* __restrict__ partials) {

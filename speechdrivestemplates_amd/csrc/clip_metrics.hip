@@ -10,12 +10,10 @@
 //   over the clips   chunks of 64 clips in index order, then the chunk partials in order.
 // Every multiply, add and subtract goes through sdt_exact::mul_rn / add_rn / sub_rn (no FMA); counts are integers.  No floating-point atomics:
 // the only atomic is the integer count of clip indices outside the table.
-#include "exact_f64.h"
+#include "record_table.h"
 
-using sdt_exact::add_rn;
-using sdt_exact::div_rn;
-using sdt_exact::mul_rn;
-using sdt_exact::sub_rn;
+using namespace sdt_exact;
+using namespace sdt_table;
 
 namespace {
 
@@ -24,8 +22,6 @@ constexpr int kFrameWords = 32;               // per-frame partial: 16 float64 s
 constexpr int kMaxK = 128;
 constexpr int kMaxCopies = 16;
 constexpr int kMaxAlphas = 4;
-constexpr int kMaxRanks = 64;
-constexpr int kChunk = 64;       // clips per chunk of the epoch sum
 constexpr int kChunkWords = 48;  // per-chunk partial: the 36 summed record words and the counters below
 // words of a chunk partial beyond the record's sums: 36 clips with a record, 37 sum of copies * frames, 38 clips left out as nonfinite,
 // 39 sum of copies * (frames - 1), 40 sum of copies (copies - 1) / 2 * frames
@@ -34,23 +30,9 @@ constexpr int kSeen = 36, kCopies = 37, kNonfinite = 38, kFrames = 39, kPairFram
 struct Alphas {
     double a[kMaxAlphas];
 };
-struct Tables {
-    const int64_t* t[kMaxRanks];
-};
 struct PartSizes {
     int64_t n[4];
 };
-
-__device__ __forceinline__ double butterfly_sum(double v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = add_rn(v, __shfl_xor(v, o, 64));
-    return v;
-}
-__device__ __forceinline__ double norm2(double x, double y) { return add_rn(mul_rn(x, x), mul_rn(y, y)); }
-__device__ __forceinline__ bool in_part(int p, int part) { return p == 0 || part == p - 1; }
-__device__ __forceinline__ int64_t bits_of(double v) { return __double_as_longlong(v); }
-__device__ __forceinline__ double double_of(int64_t v) { return __longlong_as_double(v); }
-__device__ __forceinline__ bool finite_d(double v) { return fabs(v) < __builtin_huge_val(); }  // false for NaN and +-inf
 
 // one workgroup of 128 threads per (row, frame); thread k handles keypoint k
 __global__ __launch_bounds__(128) void clip_rows_frame_kernel(const double* __restrict__ pred, const double* __restrict__ gt,
@@ -193,7 +175,7 @@ __global__ __launch_bounds__(64) void clip_commit_kernel(const int64_t* __restri
     const bool nonfinite = __ballot((c < 20 && !finite_d(s)) || (c == kNonfinite && h != 0)) != 0;
     const int64_t idx = clip_index[b];
     if (idx < 0 || idx >= N) {  // writes nothing but the header's count
-        if (c == 0) atomicAdd(reinterpret_cast<unsigned long long*>(table + (size_t)N * kCols), 1ull);
+        if (c == 0) count_index_error(table, N, kCols);
         return;
     }
     int64_t* out = table + (size_t)idx * kCols;
@@ -212,11 +194,7 @@ __global__ __launch_bounds__(64) void clip_epoch_chunk_kernel(Tables tb, int ran
     double s = 0.0;
     int64_t h = 0;
     for (int64_t n = n0; n < n1; ++n) {
-        const int64_t* rec = nullptr;
-        for (int r = 0; r < ranks && !rec; ++r) {
-            const int64_t* cand = tb.t[r] + (size_t)n * kCols;
-            if (cand[kSeen] != 0) rec = cand;
-        }
+        const int64_t* rec = first_seen(tb, ranks, n, kCols, kSeen);
         if (!rec) continue;
         const bool bad = rec[kNonfinite] != 0;
         const int64_t copies = rec[kCopies], frames = rec[kFrames];
@@ -233,27 +211,15 @@ __global__ __launch_bounds__(64) void clip_epoch_chunk_kernel(Tables tb, int ran
     if (c < kChunkWords) work[(size_t)blockIdx.x * kChunkWords + c] = c < 20 ? bits_of(s) : h;
 }
 
-__device__ __forceinline__ double quotient(double x, int64_t n) { return n == 0 ? 0.0 : div_rn(x, (double)n); }
-
 // one wave: the chunk partials in order, then the divisions
 __global__ __launch_bounds__(64) void clip_epoch_final_kernel(Tables tb, int ranks, int64_t N, const int64_t* __restrict__ work, int64_t chunks,
                                                               PartSizes ps, int A, int64_t* __restrict__ out) {
     __shared__ int64_t tot[kChunkWords];
     __shared__ int64_t errors;
     const int c = threadIdx.x;
-    if (c < 20) {
-        double s = 0.0;
-        for (int64_t i = 0; i < chunks; ++i) s = add_rn(s, double_of(work[(size_t)i * kChunkWords + c]));
-        tot[c] = bits_of(s);
-    } else if (c < kChunkWords) {
-        int64_t h = 0;
-        for (int64_t i = 0; i < chunks; ++i) h += work[(size_t)i * kChunkWords + c];
-        tot[c] = h;
-    } else if (c == kChunkWords) {
-        int64_t e = 0;
-        for (int r = 0; r < ranks; ++r) e += tb.t[r][(size_t)N * kCols];
-        errors = e;
-    }
+    if (c < 20) tot[c] = bits_of(chunk_sum_f64(work, chunks, kChunkWords, c));
+    else if (c < kChunkWords) tot[c] = chunk_sum_i64(work, chunks, kChunkWords, c);
+    else if (c == kChunkWords) errors = index_errors(tb, ranks, N, kCols);
     __syncthreads();
     const int p = c & 3;
     const int64_t n_pos = tot[kCopies] * ps.n[p], n_vel = tot[kFrames] * ps.n[p], n_div = tot[kPairFrames] * ps.n[p];
@@ -336,10 +302,7 @@ extern "C" int sdt_clip_metrics_epoch(const void* const* tables, int ranks, int6
     SDT_CHECK_ARG(num_alphas >= 1 && num_alphas <= kMaxAlphas, "number of alphas outside [1, 4]");
     Tables tb;
     PartSizes ps;
-    for (int r = 0; r < kMaxRanks; ++r) {
-        SDT_CHECK_ARG(r >= ranks || tables[r], "null table");
-        tb.t[r] = r < ranks ? (const int64_t*)tables[r] : nullptr;
-    }
+    SDT_CHECK_ARG(fill_tables(tb, tables, ranks), "null table");
     for (int p = 0; p < 4; ++p) {
         SDT_CHECK_ARG(part_sizes[p] >= 0 && part_sizes[p] <= kMaxK, "part size outside [0, 128]");
         ps.n[p] = part_sizes[p];

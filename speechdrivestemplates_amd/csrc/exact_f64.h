@@ -1,4 +1,5 @@
-// float64 device arithmetic that is reproducible to the bit, shared by speaker_stats.hip, code_pca.hip, code_axes.hip, fgd.hip and jacobi.h:
+// float64 device arithmetic that is reproducible to the bit, shared by speaker_stats.hip, code_pca.hip, code_axes.hip, fgd.hip, jacobi.h and,
+// through exact_lanes.h (the lane helpers) and record_table.h, by clip_metrics.hip, sync_metrics.hip, long_demo.hip and augment.hip:
 // the four operations each rounded on its own, the ordered sum, and the constants and the triangle indexing of the 64-wide problem.
 #pragma once
 #include "common.h"

@@ -15,12 +15,9 @@
 //   seam             every lane adds its pair terms in lexicographic (i, j) order from +0.0 before the butterfly;
 //   over the frames  chunks of 64 frames, serially in ascending t from +0.0, then the chunk partials in order.
 // Every multiply, add, subtract and divide goes through sdt_exact::*_rn (no FMA); counts are integers.  No atomics.
-#include "exact_f64.h"
+#include "exact_lanes.h"
 
-using sdt_exact::add_rn;
-using sdt_exact::div_rn;
-using sdt_exact::mul_rn;
-using sdt_exact::sub_rn;
+using namespace sdt_exact;
 
 namespace {
 
@@ -60,15 +57,6 @@ __device__ __forceinline__ int weight(const Layout& g, int t, int s) {
     const int a = t - s + 1, b = s + g.W - t, u = a < b ? a : b, R = g.O > 1 ? g.O : 1;
     return u < R ? u : R;
 }
-
-__device__ __forceinline__ double butterfly_sum(double v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = add_rn(v, __shfl_xor(v, o, 64));
-    return v;
-}
-__device__ __forceinline__ double norm2(double x, double y) { return add_rn(mul_rn(x, x), mul_rn(y, y)); }
-__device__ __forceinline__ bool in_part(int p, int part) { return p == 0 || part == p - 1; }
-__device__ __forceinline__ bool finite_d(double v) { return fabs(v) < __builtin_huge_val(); }  // false for NaN and +-inf
 
 // out[i][j] = audio[offsets[i] + j], 0.0f at or past the end of the recording (and before its start)
 __global__ __launch_bounds__(256) void long_gather_kernel(const float* __restrict__ audio, int64_t L, const int64_t* __restrict__ offsets, int Lw,

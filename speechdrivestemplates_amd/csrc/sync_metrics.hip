@@ -13,12 +13,10 @@
 //   over the copies  j = 0 .. m-1; over the clips: chunks of 64 clips in index order, then the chunk partials in order.
 // Every multiply, add, subtract and divide goes through sdt_exact (no FMA); counts and distances are integers.  No floating-point atomics: the
 // only atomic is the integer count of clip indices outside the table.
-#include "exact_f64.h"
+#include "record_table.h"
 
-using sdt_exact::add_rn;
-using sdt_exact::div_rn;
-using sdt_exact::mul_rn;
-using sdt_exact::sub_rn;
+using namespace sdt_exact;
+using namespace sdt_table;
 
 namespace {
 
@@ -32,8 +30,6 @@ constexpr int kCols = SDT_SYNC_COLS;          // words of a clip record
 constexpr int kOutCols = SDT_SYNC_OUT_COLS;   // words of the epoch vector
 constexpr int kMaxK = 128;
 constexpr int kMaxCopies = 16;
-constexpr int kMaxRanks = 64;
-constexpr int kChunk = 64;                    // clips per chunk of the epoch sum
 constexpr int kMaxHops = 1 << 28;             // 3 n + 3 stays an int32
 constexpr int kMaxFrames = 1 << 24;
 // words of a clip record (and of a chunk partial): float64 [0,4) align of the prediction, [4,8) of the ground truth; int64 [8,24) beats, hits,
@@ -42,20 +38,6 @@ constexpr int kOnsets = 40, kSeen = 41, kCopies = 42, kNonfinite = 43, kFrames =
 // words of a row record: float64 [0,4) align; int64 [4,20) beats, hits, dsum, covered per part
 constexpr int kRowOnsets = 20, kRowNonfinite = 21, kRowFrames = 22;
 
-struct Tables {
-    const int64_t* t[kMaxRanks];
-};
-
-__device__ __forceinline__ double butterfly_sum(double v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = add_rn(v, __shfl_xor(v, o, 64));
-    return v;
-}
-__device__ __forceinline__ int64_t butterfly_count(int64_t v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
 // the value lane i holds (i is the same in every lane)
 __device__ __forceinline__ double lane_value(double v, int i) {
     const int lo = __builtin_amdgcn_readlane(__double2loint(v), i), hi = __builtin_amdgcn_readlane(__double2hiint(v), i);
@@ -67,11 +49,6 @@ __device__ __forceinline__ double add_lanes_in_order(double s, double v) {
     for (int i = 0; i < 64; ++i) s = add_rn(s, lane_value(v, i));
     return s;
 }
-__device__ __forceinline__ double norm2(double x, double y) { return add_rn(mul_rn(x, x), mul_rn(y, y)); }
-__device__ __forceinline__ bool in_part(int p, int part) { return p == 0 || part == p - 1; }
-__device__ __forceinline__ int64_t bits_of(double v) { return __double_as_longlong(v); }
-__device__ __forceinline__ double double_of(int64_t v) { return __longlong_as_double(v); }
-__device__ __forceinline__ bool finite_d(double v) { return fabs(v) < __builtin_huge_val(); }  // false for NaN and +-inf
 
 // four waves per workgroup, one wave per audio frame; blockIdx.y is the clip
 __global__ __launch_bounds__(256) void sync_envelope_kernel(const float* __restrict__ audio, int64_t L, int Nf, double* __restrict__ env) {
@@ -304,7 +281,7 @@ __global__ __launch_bounds__(64) void sync_commit_kernel(const int64_t* __restri
     const bool nonfinite = __ballot((c < 8 && !finite_d(s)) || (c == kNonfinite && h != 0)) != 0;
     const int64_t idx = clip_index[b];
     if (idx < 0 || idx >= N) {  // writes nothing but the header's count
-        if (c == 0) atomicAdd(reinterpret_cast<unsigned long long*>(table + (size_t)N * kCols), 1ull);
+        if (c == 0) count_index_error(table, N, kCols);
         return;
     }
     if (c >= kCols) return;
@@ -326,11 +303,7 @@ __global__ __launch_bounds__(64) void sync_epoch_chunk_kernel(Tables tb, int ran
     double s = 0.0;
     int64_t h = 0;
     for (int64_t n = n0; n < n1; ++n) {
-        const int64_t* rec = nullptr;
-        for (int r = 0; r < ranks && !rec; ++r) {
-            const int64_t* cand = tb.t[r] + (size_t)n * kCols;
-            if (cand[kSeen] != 0) rec = cand;
-        }
+        const int64_t* rec = first_seen(tb, ranks, n, kCols, kSeen);
         if (!rec) continue;
         const bool bad = rec[kNonfinite] != 0;
         if (c == kSeen) h += 1;
@@ -345,27 +318,15 @@ __global__ __launch_bounds__(64) void sync_epoch_chunk_kernel(Tables tb, int ran
     if (c < kCols) work[(size_t)blockIdx.x * kCols + c] = c < 8 ? bits_of(s) : h;
 }
 
-__device__ __forceinline__ double quotient(double x, int64_t n) { return n == 0 ? 0.0 : div_rn(x, (double)n); }
-
 // one wave: the chunk partials in order, then the divisions
 __global__ __launch_bounds__(64) void sync_epoch_final_kernel(Tables tb, int ranks, int64_t N, const int64_t* __restrict__ work, int64_t chunks,
                                                               int64_t* __restrict__ out) {
     __shared__ int64_t tot[kCols];
     __shared__ int64_t errors;
     const int c = threadIdx.x;
-    if (c < 8) {
-        double s = 0.0;
-        for (int64_t i = 0; i < chunks; ++i) s = add_rn(s, double_of(work[(size_t)i * kCols + c]));
-        tot[c] = bits_of(s);
-    } else if (c < kCols) {
-        int64_t h = 0;
-        for (int64_t i = 0; i < chunks; ++i) h += work[(size_t)i * kCols + c];
-        tot[c] = h;
-    } else if (c == kCols) {
-        int64_t e = 0;
-        for (int r = 0; r < ranks; ++r) e += tb.t[r][(size_t)N * kCols];
-        errors = e;
-    }
+    if (c < 8) tot[c] = bits_of(chunk_sum_f64(work, chunks, kCols, c));
+    else if (c < kCols) tot[c] = chunk_sum_i64(work, chunks, kCols, c);
+    else if (c == kCols) errors = index_errors(tb, ranks, N, kCols);
     __syncthreads();
     if (c >= kOutCols) return;
     const int p = (c & 1) ? 3 : 0, q = c >> 1;  // value q for all (even words) and for hands (odd words)
@@ -455,10 +416,7 @@ extern "C" int sdt_sync_epoch(const void* const* tables, int ranks, int64_t N, v
     SDT_CHECK_ARG(ranks >= 1 && ranks <= kMaxRanks, "tables outside [1, 64]");
     SDT_CHECK_ARG(N >= 1 && cdiv64(N, kChunk) <= 0x7fffffff, "bad number of clips");
     Tables tb;
-    for (int r = 0; r < kMaxRanks; ++r) {
-        SDT_CHECK_ARG(r >= ranks || tables[r], "null table");
-        tb.t[r] = r < ranks ? (const int64_t*)tables[r] : nullptr;
-    }
+    SDT_CHECK_ARG(fill_tables(tb, tables, ranks), "null table");
     const int64_t chunks = cdiv64(N, kChunk);
     hipStream_t s = (hipStream_t)stream;
     hipLaunchKernelGGL(sync_epoch_chunk_kernel, dim3((unsigned)chunks), dim3(64), 0, s, tb, ranks, N, (int64_t*)work);

@@ -22,15 +22,14 @@ stitches an (N, W, 2, K) array of window poses (``poses_windows`` of a DEMO npz)
 """
 import numpy as np
 
-from .clip_metrics import LANES, PARTS, _norm2, _ordered_sum, _part_sums, check_parts, part_sizes
+from ._exact_model import MAX_K, PARTS, _norm2, _ordered_sum, _part_sums, _quotient, check_parts, part_sizes
 
 COLS = 40  # words of the report (SDT_LONG_REPORT_COLS)
 GROUPS = ('speed', 'jerk', 'speed_smoothed', 'jerk_smoothed', 'seam')  # float64 words [0, 20): group g, part p at 4 g + p
 N_SPEED, N_JERK, N_SEAM, NONFINITE, FRAMES, WINDOWS, SMOOTHED, PAIR_FRAMES = 20, 24, 28, 32, 33, 34, 35, 36  # int64 words
-MAX_K, MAX_HALF, CHUNK, MAX_FRAMES = 128, 8, 64, 1 << 24
+MAX_HALF, CHUNK, MAX_FRAMES = 8, 64, 1 << 24
 _NO_GPU = 'the long-form demo is computed on the GPU (csrc/long_demo.hip); there is no CPU fallback (stitch_model / smooth_model / ' \
           'report_model are the numpy contract)'
-assert LANES == MAX_K
 
 
 # ---- layout: integers only, shared by the host module and the models ---------------------------------------------------------------------------
@@ -155,10 +154,6 @@ def _motion_terms(x):
         d = ((x[3:] - 3.0 * x[2:-1]) + 3.0 * x[1:-2]) - x[:-3]
         jerk[:F - 3] = np.sqrt(_norm2(d[:, 0], d[:, 1]))
     return speed, jerk
-
-
-def _quotient(x, n):
-    return np.float64(0.0) if n == 0 else np.float64(x) / np.float64(n)
 
 
 def report_model(windows, stitched, smoothed, O, parts=None, return_sums=False):

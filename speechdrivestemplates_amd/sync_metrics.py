@@ -21,15 +21,21 @@ csrc/sync_metrics.hip on CUDA tensors.  There is no CPU fallback.
 reads ``poses_pred_batch`` (and ``poses_gt_batch`` if present) of a results npz, (R, T, 2, K), and the audio of those R clips ((R, L) or (L,)
 float samples at 16000 Hz; a wav file is one clip), runs the device route and prints the epoch values.
 """
+from functools import partial
+
 import numpy as np
 
-from .clip_metrics import MAX_COPIES, MAX_K, MAX_TABLES, PARTS, _norm2, _part_sums, check_parts
+from . import _record_table
+from ._exact_model import MAX_TABLES  # noqa: F401  (public names of this module)
+from ._exact_model import MAX_COPIES, MAX_K, PARTS, _butterfly_wave, _norm2, _ordered_sum, _part_sums, _quotient, check_parts
+from ._record_table import CHUNK  # noqa: F401
+from ._record_table import RecordTable, check_num_clips, chunked_records
 
 SAMPLE_RATE, FPS, TICKS = 16000, 15, 300
 HOP, FRAME, HOP_TICKS, FRAME_TICKS = 160, 320, 3, 20
 HALF, GAP, DMAX = 15, 8, 150
 DELTA, FLOOR, GAMMA = 1.5, 2.0 ** -6, 1.0  # untuned detector constants (handed to the launches by value)
-ROW_COLS, COLS, OUT_COLS, CHUNK = 24, 48, 24, 64  # SDT_SYNC_ROW_COLS, SDT_SYNC_COLS, SDT_SYNC_OUT_COLS
+ROW_COLS, COLS, OUT_COLS = 24, 48, 24  # SDT_SYNC_ROW_COLS, SDT_SYNC_COLS, SDT_SYNC_OUT_COLS
 INT_GROUPS = ('beats', 'hits', 'dsum', 'covered')
 ROW_ONSETS, ROW_NONFINITE, ROW_FRAMES = 20, 21, 22  # a row record: float64 [0,4) align[p]; int64 [4,20) group g, part p at 4 + 4 g + p
 ALIGN_PRED, ALIGN_GT, INT_PRED, INT_GT = 0, 4, 8, 24  # a clip record: float64 [0,8); int64 group g, part p at 8 (or 24) + 4 g + p
@@ -97,10 +103,7 @@ def envelope_model(audio, return_energy=False):
         for j in range(5):  # lane l: samples l, l + 64, .., l + 256; the first product starts the sum
             v = pad[idx + 64 * j]
             acc = v * v if acc is None else acc + v * v
-        lanes = np.arange(64)
-        for o in (32, 16, 8, 4, 2, 1):
-            acc = acc + acc[:, lanes ^ o]
-        energy = acc[:, 0] if Nf else np.zeros(0)
+        energy = _butterfly_wave(acc)
         return (np.sqrt(energy), energy) if return_energy else np.sqrt(energy)
 
 
@@ -150,14 +153,6 @@ def speeds_model(poses, parts):
         return _part_sums(np.sqrt(_norm2(x[:, 1:, 0] - x[:, :-1, 0], x[:, 1:, 1] - x[:, :-1, 1])), parts)
 
 
-def _serial_sum(x):
-    """(n, ...) -> the sum along axis 0 in order from +0.0"""
-    s = np.zeros(x.shape[1:])
-    for i in range(x.shape[0]):
-        s = s + x[i]
-    return s
-
-
 def beats_model(poses, parts=None, gamma=GAMMA):
     """(R, T, 2, K) float64 -> {'speed': (R, T - 1, 4), 'flags': (R, 4, T) bool, 'nonfinite': (R,) bool}; ``beat_ticks`` lists the ticks"""
     s = speeds_model(poses, parts)
@@ -165,7 +160,7 @@ def beats_model(poses, parts=None, gamma=GAMMA):
     T = np.asarray(poses).shape[1]
     flags = np.zeros((R, 4, T), dtype=bool)
     with np.errstate(all='ignore'):
-        total = _serial_sum(np.moveaxis(s, 1, 0))  # (R, 4)
+        total = _ordered_sum(s, 1)  # (R, 4)
         if T >= 4:
             thr = np.float64(gamma) * (total / np.float64(Tm1))
             mid = s[:, 1:Tm1 - 1]
@@ -233,7 +228,7 @@ def sync_model(pred, gt, audio, parts, tol, table, multiple=1, delta=DELTA, floo
     rec = np.zeros((B, COLS), dtype=np.int64)
     for w, (a0, i0) in enumerate(((ALIGN_PRED, INT_PRED), (ALIGN_GT, INT_GT))):
         copies = rows[w].reshape(m, B, ROW_COLS)
-        rec[:, a0:a0 + 4] = _serial_sum(copies[:, :, :4].copy().view(np.float64)).view(np.int64)
+        rec[:, a0:a0 + 4] = _ordered_sum(copies[:, :, :4].copy().view(np.float64), 0).view(np.int64)
         rec[:, i0:i0 + 16] = copies[:, :, 4:20].sum(axis=0)
         rec[:, NONFINITE] += copies[:, :, ROW_NONFINITE].sum(axis=0)
     rec[:, ONSETS] = rows[0].reshape(m, B, ROW_COLS)[:, :, ROW_ONSETS].sum(axis=0)
@@ -242,22 +237,13 @@ def sync_model(pred, gt, audio, parts, tol, table, multiple=1, delta=DELTA, floo
     return rec
 
 
-def _quotient(x, n):
-    return np.float64(0.0) if n == 0 else np.float64(x) / np.float64(n)
-
-
 def epoch_model(tables, index_errors=0):
     """the 24 words of sdt_sync_epoch over ``tables``, a list of (N, 48) int64 record arrays, one per rank"""
-    tables = [np.asarray(t, dtype=np.int64) for t in tables]
-    N = tables[0].shape[0]
     tot_f, tot_i = np.zeros(8), np.zeros(COLS, dtype=np.int64)
     with np.errstate(all='ignore'):
-        for n0 in range(0, N, CHUNK):
+        for chunk in chunked_records(tables, SEEN):
             f, h = np.zeros(8), np.zeros(COLS, dtype=np.int64)
-            for n in range(n0, min(N, n0 + CHUNK)):
-                rec = next((t[n] for t in tables if t[n, SEEN] != 0), None)
-                if rec is None:
-                    continue
+            for rec in chunk:
                 h[SEEN] += 1
                 if rec[NONFINITE] != 0:
                     h[NONFINITE] += 1
@@ -298,14 +284,7 @@ def epoch_values(words):
     return out
 
 
-def merge_tables(tables):
-    """(N, 48) record arrays, one per rank -> the records the epoch stage reads: per clip the lowest rank that has seen it"""
-    tables = [np.asarray(t, dtype=np.int64) for t in tables]
-    out = np.zeros_like(tables[0])
-    for t in tables:
-        take = (out[:, SEEN] == 0) & (t[:, SEEN] != 0)
-        out[take] = t[take]
-    return out
+merge_tables = partial(_record_table.merge_tables, seen=SEEN)  # (tables) -> per clip the record of the lowest rank that has seen it
 
 
 def save_table(path, records, tol, sigma):
@@ -409,25 +388,19 @@ class _Device:
                                                self._p(work), self._p(rows), self._stream()))
 
 
-class SyncAccumulator:
+class SyncAccumulator(RecordTable):
     """A table of ``num_clips`` clip records on ``device`` and its epoch values.
 
     ``add`` enqueues the launches of one validation step on the current stream (the detector: envelope, onsets; per pose tensor: speeds,
     beats-and-matching; one commit): no host synchronisation, and no allocation once the workspace has the step's shape.  ``result`` is the
     only call that waits for the device.  The state is one (num_clips + 1, 48) int64 tensor: the records, then a header row whose word 0
-    counts the clip indices outside the table."""
+    counts the clip indices outside the table (``RecordTable`` owns it, ``state``, ``table``, ``reset``, ``result`` and ``result_words``)."""
 
     def __init__(self, num_clips, K, tol_ticks, sigma, device='cuda', parts=None):
-        num_clips = int(num_clips)
-        if num_clips < 1:
-            raise ValueError('the table needs at least one clip, got %d' % num_clips)
+        num_clips = check_num_clips(num_clips)
         self._dev = _Device(K, tol_ticks, gauss_table(sigma), device, parts)
-        torch = self._dev._torch
-        self.num_clips, self.K, self.tol, self.sigma, self.parts, self.device = num_clips, self._dev.K, self._dev.tol, float(sigma), \
-            self._dev.parts, self._dev.device
-        self._state = torch.zeros((num_clips + 1, COLS), dtype=torch.int64, device=self.device)
-        self._epoch_work = torch.empty((-(-num_clips // CHUNK), COLS), dtype=torch.int64, device=self.device)
-        self._out = torch.empty(OUT_COLS, dtype=torch.int64, device=self.device)
+        self.K, self.tol, self.sigma, self.parts = self._dev.K, self._dev.tol, float(sigma), self._dev.parts
+        RecordTable.__init__(self, num_clips, self._dev.device, COLS, COLS, OUT_COLS)
 
     def add(self, pred, gt, audio, clip_index, multiple=1):
         """one validation step: rows (multiple * B, T, 2, K) of final poses, copy j of clip b in row j * B + b (``gt`` may be None); ``audio``
@@ -459,41 +432,12 @@ class SyncAccumulator:
             _lib.check(d._lib.sdt_sync_commit(d._p(bufs[3]), None if gt is None else d._p(bufs[4]), d._p(idx), B, m, T, audio.shape[1],
                                               d._p(self._state), self.num_clips, d._stream()))
 
-    def state(self):
-        """the (num_clips + 1, 48) int64 tensor (records, then the header row), for a collective"""
-        return self._state
+    def _launch_epoch(self, ptrs, ranks, stream):
+        d = self._dev
+        return d._lib.sdt_sync_epoch(ptrs, ranks, self.num_clips, d._p(self._epoch_work), d._p(self._out), stream)
 
-    def table(self):
-        """the (num_clips, 48) records, a view of the state"""
-        return self._state[:self.num_clips]
-
-    def reset(self):
-        self._state.zero_()
-
-    def result(self, gathered=None):
-        """-> the named epoch values (``epoch_values``) over this accumulator's table, or over ``gathered``: a (ranks, num_clips + 1, 48) int64
-        tensor (or a list of such states / accumulators), one entry per rank; the lowest rank that has seen a clip gives its record"""
-        return epoch_values(self.result_words(gathered))
-
-    def result_words(self, gathered=None):
-        """the 24 words of the epoch vector as a numpy int64 array (float64 words viewed as int64)"""
-        from . import _lib
-        d, torch = self._dev, self._dev._torch
-        if gathered is None:
-            blocks = [self._state]
-        elif torch.is_tensor(gathered):
-            blocks = list(gathered.unbind(0)) if gathered.ndim == 3 else [gathered]
-        else:
-            blocks = [g.state() if isinstance(g, SyncAccumulator) else g for g in gathered]
-        if not 1 <= len(blocks) <= MAX_TABLES:
-            raise ValueError('%d tables; the epoch stage takes 1 to %d' % (len(blocks), MAX_TABLES))
-        for b in blocks:
-            if b.dtype != torch.int64 or tuple(b.shape) != tuple(self._state.shape) or b.device != self.device or not b.is_contiguous():
-                raise ValueError('a gathered state must be a contiguous %s int64 tensor on %s' % (tuple(self._state.shape), self.device))
-        ptrs = (d._C.c_void_p * len(blocks))(*[b.data_ptr() for b in blocks])
-        with torch.cuda.device(self.device):
-            _lib.check(d._lib.sdt_sync_epoch(ptrs, len(blocks), self.num_clips, d._p(self._epoch_work), d._p(self._out), d._stream()))
-            return self._out.cpu().numpy()  # (same stream: ordered after the kernels, and the one wait of this class)
+    def epoch_values(self, words):
+        return epoch_values(words)
 
 
 def _cuda(x, what):
