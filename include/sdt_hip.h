@@ -1069,6 +1069,37 @@ int sdt_augment_audio_f32(const float* audio, int B, int64_t L, const int64_t* c
 int sdt_augment_mel_mask_f32(float* mel, int B, int M, int F, const int64_t* clip_index, const int64_t* step, uint64_t seed, int nf, int wf, int nt,
                              int wt, void* rec, void* stream);
 
+/*
+ * Pose augmentation inside the train step (TRAIN.POSE_AUGMENT; speechdrivestemplates_amd/pose_augment.py; DESIGN.md section 30 is the
+ * contract, pose_augment.params_model / pose_model are the same operations in numpy; no counterpart in the reference): a left/right mirror
+ * about the neck, a per-clip uniform scale and a per-clip in-plane rotation about the neck.  One Philox4x32-10 block per clip (the generator of
+ * the audio augmentation above): key (seed low 32 bits, seed high 32 bits), counter (0, purpose 2, clip_index[b] low 32 bits, step[0] low
+ * 32 bits -- 0 with per_clip).  mirror = (w0 >> 8) < mirror_prob24 (0 .. 2^24); is = w1 >> 24, s = scale_table[is] (256 float64);
+ * ir = w2 >> 24, (c, sn) = rot_table[2 ir], rot_table[2 ir + 1] (256 float64 pairs); w3 is unused.  No transcendental function, no
+ * allocation, no host synchronisation, no atomics, no scratch; clip_index (B,) and step (1,) are int64 device buffers read by the kernels,
+ * so a captured graph follows them.  perm is a HOST array of K int32, the mirror partner of each keypoint: it is checked to be a
+ * permutation of 0 .. K - 1 (else SDT_ERR_ARG) and travels to the kernel by value.  Sizes: K in [1, 128], B in [1, 65535], T in [1, 2^24],
+ * n_clips in [1, 2^40]; anything else returns SDT_ERR_UNSUPPORTED before any launch.  Out of place: poses_out != poses, score_out != score.
+ *   poses, poses_out (B, T, 2, K) float32 (x row, y row per frame); score_or_null, score_out the same shape (score_out unused without a
+ *   score); mean, std (B, 2 K) float64 (x then y).  For keypoint k with m = perm[k] under mirror and m = k without, per frame, in float64 on
+ *   values converted exactly from float32, every multiply, add, subtract and divide rounded on its own (csrc/exact_f64.h):
+ *     dx = n_x[m] std_x[m] + mean_x[m], dy likewise; dx = -dx under mirror;
+ *     (rx, ry) = (s dx, s dy) when c == 1 and sn == 0 (no rotation: the coordinates stay apart), else
+ *     (rx, ry) = (s (c dx - sn dy), s (sn dx + c dy));
+ *     out_x[k] = float32((rx - mean_x[k]) / std_x[k]), out_y[k] likewise.
+ *   A clip whose transformation is the identity (no mirror, s == 1, c == 1, sn == 0) gets its input's bits instead.  score_out[.][k] =
+ *   score[.][m] as bits.  eff_index[b] = clip_index[b] + n_clips * mirror.  A non-finite input element reaches only the outputs of the
+ *   keypoint k with perm[k] = its keypoint, in its frame: its own coordinate, and both with a rotation on.
+ *   rec (B, SDT_POSE_AUGMENT_REC_COLS) words of 8 bytes: int64 0 mirror, 1 is, 2 ir, float64 3 s, 4 c, 5 sn, int64 6 the effective index,
+ *   7 identity.  One launch of a thread per clip, one of a thread per (frame, keypoint) with plain dword accesses (rows of 2 K floats are not
+ *   16-byte aligned).
+ */
+#define SDT_POSE_AUGMENT_REC_COLS 8
+int sdt_pose_augment_f32(const float* poses, const float* score_or_null, const double* mean, const double* std, int B, int T, int K,
+                         const int64_t* clip_index, const int64_t* step, int64_t n_clips, uint64_t seed, int64_t mirror_prob24, int per_clip,
+                         const int32_t* perm, const double* scale_table, const double* rot_table, float* poses_out, float* score_out,
+                         int64_t* eff_index, void* rec, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -213,6 +213,7 @@ SIGNATURES = {
     "sdt_augment_sumsq_f64": [_p, _i, _i64, _p, _p, _p],
     "sdt_augment_audio_f32": [_p, _i, _i64, _p, _p, _p, C.c_uint64, _i64, _i64, _i, _p, _p, _p, _p, _p],
     "sdt_augment_mel_mask_f32": [_p, _i, _i, _i, _p, _p, C.c_uint64, _i, _i, _i, _i, _p, _p],
+    "sdt_pose_augment_f32": [_p, _p, _p, _p, _i, _i, _i, _p, _p, _i64, C.c_uint64, _i64, _i, C.POINTER(C.c_int32), _p, _p, _p, _p, _p, _p, _p],
 }
 F32, BF16 = 0, 1  # enum sdt_dtype
 

@@ -77,7 +77,18 @@ _DEFAULTS = {
               # flip per clip.  MEL_FREQ_MASKS [n, w]: n in 0 .. 4 bands of 0 .. w (at most 40) mel bins set to 0; MEL_TIME_MASKS [n, w]:
               # n in 0 .. 4 spans of 0 .. w (at most 100) mel columns set to 0.
               "AUGMENT": {"ENABLE": False, "SEED": 0, "GAIN_DB": 0.0, "NOISE_SNR_DB": None, "NOISE_PROB": 1.0, "SHIFT_MS": 0.0,
-                          "POLARITY": False, "MEL_FREQ_MASKS": [0, 0], "MEL_TIME_MASKS": [0, 0]}},
+                          "POLARITY": False, "MEL_FREQ_MASKS": [0, 0], "MEL_TIME_MASKS": [0, 0]},
+              # extension (pose augmentation inside the train step, pose_augment.PoseAugmenter / csrc/pose_augment.hip; DESIGN.md section 30;
+              # Voice2Pose and Pose2Pose; needs DATASET.NUM_LANDMARKS 121; off by default = the step as it was, no kernel launched, the code
+              # tables as large as they were).  With ENABLE the training forward pass hands the batch's poses (and their confidences) through
+              # one GPU pass before anything reads them; evaluation, the demo and bench.py see untouched poses.  Everything random is one
+              # Philox4x32-10 block of (SEED, global step, clip index), purpose 2 beside the audio augmenter's 0 and 1.
+              # SEED: integer in [0, 2^64).  MIRROR_PROB in [0, 1]: the share of draws that mirror the skeleton left/right about the neck
+              # (PoseTransforms.mirror_table); with MIRROR_PROB > 0 the per-clip code tables have 2 N rows and a mirrored clip i trains row
+              # N + i.  SCALE_PCT p in [0, 50]: a per-clip uniform scale, 256 levels in [1 - p / 100, 1 + p / 100].  ROT_DEG r in [0, 45]: a
+              # per-clip in-plane rotation about the neck, 256 levels in [-r, +r] degrees.  PER_CLIP True: the step is left out of the draw,
+              # so a clip gets the same transformation at every step (a fixed transformation of the data set).
+              "POSE_AUGMENT": {"ENABLE": False, "SEED": 0, "MIRROR_PROB": 0.0, "SCALE_PCT": 0.0, "ROT_DEG": 0.0, "PER_CLIP": False}},
     "TEST": {"BATCH_SIZE": 32, "NUM_RESULT_SAMPLE": 8, "SAVE_VIDEO": True, "SAVE_NPZ": True, "MULTIPLE": 1,
              # extensions (per-clip validation metrics, clip_metrics.ClipMetricsAccumulator / csrc/clip_metrics.hip; DESIGN.md section 22;
              # Voice2Pose only).  CLIP_METRICS True = every test_step also commits its clips' records (keypoint-distance, PCK-hit, speed,
@@ -388,6 +399,41 @@ def check_augment(cfg):
     return {'seed': int(seed), 'gain_db': float(gain), 'snr': None if snr is None else (float(snr[0]), float(snr[1])), 'noise_prob': float(prob),
             'shift_ms': float(shift), 'shift': samples, 'polarity': pol, 'freq_masks': masks["MEL_FREQ_MASKS"][:2],
             'time_masks': masks["MEL_TIME_MASKS"][:2]}
+
+
+def check_pose_augment(cfg):
+    """Validate TRAIN.POSE_AUGMENT (ValueError names the key).  With ENABLE off the other keys are checked for their type only and None is
+    returned; otherwise their ranges too, and {'seed', 'mirror_prob', 'scale_pct', 'rot_deg', 'per_clip'} comes back as Python values."""
+    a, pre = cfg.TRAIN.POSE_AUGMENT, "TRAIN.POSE_AUGMENT."
+    on, seed, prob, scale, rot, per_clip = a.ENABLE, a.SEED, a.MIRROR_PROB, a.SCALE_PCT, a.ROT_DEG, a.PER_CLIP
+    if not isinstance(on, bool):
+        raise ValueError(pre + "ENABLE must be True or False, got %r" % (on,))
+    if not _is_int(seed):
+        raise ValueError(pre + "SEED must be an integer, got %r" % (seed,))
+    for key, v in (("MIRROR_PROB", prob), ("SCALE_PCT", scale), ("ROT_DEG", rot)):
+        if not _is_number(v):
+            raise ValueError(pre + key + " must be a finite number, got %r" % (v,))
+    if not isinstance(per_clip, bool):
+        raise ValueError(pre + "PER_CLIP must be True or False, got %r" % (per_clip,))
+    if not on:
+        return None
+    if cfg.PIPELINE_TYPE not in ("Voice2Pose", "Pose2Pose"):
+        raise ValueError(pre + "ENABLE needs PIPELINE_TYPE Voice2Pose or Pose2Pose, got %r" % (cfg.PIPELINE_TYPE,))
+    if not 0 <= seed < 1 << 64:
+        raise ValueError(pre + "SEED must lie in [0, 2^64), got %r" % (seed,))
+    if not 0 <= prob <= 1:
+        raise ValueError(pre + "MIRROR_PROB must lie in [0, 1], got %r" % (prob,))
+    if not 0 <= scale <= 50:
+        raise ValueError(pre + "SCALE_PCT must lie in [0, 50], got %r" % (scale,))
+    if not 0 <= rot <= 45:
+        raise ValueError(pre + "ROT_DEG must lie in [0, 45], got %r" % (rot,))
+    if cfg.DATASET.NUM_LANDMARKS != 121:
+        raise ValueError(pre + "ENABLE needs DATASET.NUM_LANDMARKS 121 (the mirror table and the part roots are those of the 121-keypoint "
+                         "skeleton), got %r" % (cfg.DATASET.NUM_LANDMARKS,))
+    if not (prob > 0 or scale > 0 or rot > 0):
+        raise ValueError(pre + "ENABLE is set while every augmentation sits at its neutral value (MIRROR_PROB 0, SCALE_PCT 0, ROT_DEG 0): "
+                         "set one, or leave ENABLE off")
+    return {'seed': int(seed), 'mirror_prob': float(prob), 'scale_pct': float(scale), 'rot_deg': float(rot), 'per_clip': per_clip}
 
 
 def check_long_demo(cfg):

@@ -143,6 +143,40 @@ class PoseTransforms:
         return edges
 
     @staticmethod
+    def mirror_table():
+        """The left/right mirror partner of each of the 121 keypoints, a permutation that is its own inverse (pose_definition.md; TRAIN.
+        POSE_AUGMENT).  Body: the neck-relative nose 0 stays, shoulders / elbows / wrists 1 2 3 <-> 4 5 6, eyes 7 <-> 8.
+        Face (70 points from keypoint 9, the 68-point outline and two pupils): jaw i <-> 16 - i, brows 17 .. 21 <-> 26 .. 22, the bridge
+        27 .. 30 stays (30 is HEAD_ROOT), nostrils 31 .. 35 <-> 35 .. 31, eyes 36 37 38 39 40 41 <-> 45 44 43 42 47 46, outer lips 48 .. 54 <->
+        54 .. 48 and 55 .. 59 <-> 59 .. 55, inner lips 60 .. 64 <-> 64 .. 60 and 65 66 67 <-> 67 66 65, pupils 68 <-> 69.  Hands: 79 + j <->
+        100 + j, which takes the part root 6 of the left hand to the part root 3 of the right one."""
+        perm = list(range(121))
+        for a, b in ((1, 4), (2, 5), (3, 6), (7, 8)):
+            perm[a], perm[b] = b, a
+        face = list(range(70))
+        for i in range(17):
+            face[i] = 16 - i
+        for i in range(17, 27):
+            face[i] = 43 - i
+        for i in range(31, 36):
+            face[i] = 66 - i
+        for a, b in ((36, 45), (37, 44), (38, 43), (39, 42), (40, 47), (41, 46), (68, 69)):
+            face[a], face[b] = b, a
+        for i in range(48, 55):
+            face[i] = 102 - i
+        for i in range(55, 60):
+            face[i] = 114 - i
+        for i in range(60, 65):
+            face[i] = 124 - i
+        for i in range(65, 68):
+            face[i] = 132 - i
+        for i in range(70):
+            perm[9 + i] = 9 + face[i]
+        for j in range(21):
+            perm[79 + j], perm[100 + j] = 100 + j, 79 + j
+        return perm
+
+    @staticmethod
     def part_roots(hierarchical=True):
         """The part root of each of the 121 keypoints, -1 for a keypoint in no part (all of them when the poses are not hierarchical):
         ``_part_index`` as one list"""

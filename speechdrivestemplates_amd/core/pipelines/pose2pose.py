@@ -4,7 +4,8 @@ import numpy as np
 import torch
 from torch import nn
 
-from ... import dp, ops
+from ... import dp, ops, pose_augment
+from ...config import check_pose_augment
 from ...mel import MelSpectrogram
 from ...optim import FlatAdam
 from ..networks import get_model
@@ -18,12 +19,30 @@ class Pose2PoseModel(nn.Module):
         self.cfg = cfg
         self.mel_transfm = MelSpectrogram(win_length=400, hop_length=160, n_fft=512, f_min=55, f_max=7500.0, n_mels=80)
         self.ae = get_model(cfg.POSE2POSE.AUTOENCODER.NAME)(cfg)
+        # TRAIN.POSE_AUGMENT, validated; None = off: no PoseAugmenter exists, the code buffers have one row per clip
+        self.pose_aug_opts = check_pose_augment(cfg)
+        self._pose_augmenters = {}  # device -> pose_augment.PoseAugmenter, built by the first training forward pass
+        self.code_rows = None  # the rows the last training forward pass's codes belong to: clip_index + N where the clip was mirrored
+        mirrored = self.pose_aug_opts is not None and pose_augment.mirrors(self.pose_aug_opts)
         if num_train_samples is None:
             assert state_dict is not None, 'No state_dict available, while no dataset is configured.'
-            num_train_samples = state_dict['module.clip_code_mu'].shape[0]
+            rows = state_dict['module.clip_code_mu'].shape[0]
+            num_train_samples = rows // 2 if mirrored else rows
+        else:
+            rows = pose_augment.table_rows(self.pose_aug_opts, num_train_samples)
+            saved = None if state_dict is None else state_dict.get('module.clip_code_mu', state_dict.get('clip_code_mu'))
+            if saved is not None and (mirrored or saved.shape[0] == 2 * num_train_samples):
+                pose_augment.check_table_rows("the checkpoint's clip_code_mu", saved.shape[0], self.pose_aug_opts, num_train_samples)
+        self.num_clips = num_train_samples  # N: a mirrored clip i writes row N + i of the (2 N)-row buffers
         d = cfg.POSE2POSE.AUTOENCODER.CODE_DIM
-        self.register_buffer('clip_code_mu', torch.zeros([num_train_samples, d]))
-        self.register_buffer('clip_code_logvar', torch.zeros([num_train_samples, d]))
+        self.register_buffer('clip_code_mu', torch.zeros([rows, d]))
+        self.register_buffer('clip_code_logvar', torch.zeros([rows, d]))
+
+    def _pose_augmenter(self, dev):
+        key = str(dev)
+        if key not in self._pose_augmenters:
+            self._pose_augmenters[key] = pose_augment.PoseAugmenter(self.pose_aug_opts, dev, self.num_clips)
+        return self._pose_augmenters[key]
 
     def forward(self, batch, return_loss=True, is_testing=False, interpolation_coeff=None):
         dev = self.clip_code_mu.device
@@ -36,6 +55,9 @@ class Pose2PoseModel(nn.Module):
             code = torch.tensor(np.asarray(code), dtype=torch.float32, device=dev).unsqueeze(0)
             pred, mu, logvar = self.ae(None, self.cfg.DATASET.NUM_FRAMES, external_code=code)
             return {'poses_pred_batch': pred, 'clip_code_mu': mu, 'clip_code_logvar': logvar}
+        self.code_rows = None
+        if self.training and self.pose_aug_opts is not None:  # TRAIN.POSE_AUGMENT: before anything reads the poses
+            poses_gt, _, self.code_rows = pose_augment.batch_poses(self._pose_augmenter(dev), batch, dev, False)
         # the reference computes the mel spectrogram here and discards it (pose2pose.py:48, autoencoder.py:79); skipped
         pred, mu, logvar = self.ae(poses_gt, num_frames)
         reg = ops.L1LossFn.apply(pred, poses_gt, float(self.cfg.POSE2POSE.LAMBDA_REG))
@@ -77,7 +99,7 @@ class Pose2Pose(Trainer):
         _, _, metrics = ops.final_metrics(results['poses_pred_batch'].detach(), results['poses_gt_batch'], stat['mean'].to(dev),
                                           stat['std'].to(dev), stat['scale_factor'].to(dev),
                                           bool(self.cfg.DATASET.HIERARCHICAL_POSE), False)
-        idx = batch['clip_index'].to(dev)
+        idx = batch['clip_index'].to(dev) if self.model.code_rows is None else self.model.code_rows  # (a mirrored clip: its own row)
         self.model.clip_code_mu[idx] = results['clip_code_mu'].detach()  # pose2pose.py:135-137
         self.model.clip_code_logvar[idx] = results['clip_code_logvar'].detach()
         losses['L2_dist'], losses['lip_sync_error_n'] = metrics[0], metrics[1]
@@ -108,6 +130,8 @@ class Pose2Pose(Trainer):
         # SYS.RENDER_VIDEO + TRAIN.SAVE_VIDEO: save steps run eagerly and draw clip 0 (pose2pose.py:156-169); never inside a capture
         video_step = (self.rendering() and self.cfg.TRAIN.SAVE_VIDEO and self.is_master_process() and self.base_path is not None
                       and t_step % self.result_saving_interval_train == 0)
+        if self.model.pose_aug_opts is not None:  # TRAIN.POSE_AUGMENT: the step is an input of the batch, so a replayed graph follows it
+            batch = dict(batch, aug_step=torch.tensor([global_step], dtype=torch.int64))
         losses, results = self.graphed_or_eager_step(batch, eager_ok=not video_step)
         self.write_histograms(global_step)  # (SYS.HISTOGRAM_INTERVAL: after the step, outside the captured graph)
         self.last_losses = losses

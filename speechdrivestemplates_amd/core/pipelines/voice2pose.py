@@ -18,7 +18,7 @@ import torch
 from torch import nn
 
 from ... import dp, ops
-from ...config import check_augment, check_bone_loss, check_clip_metrics, check_reg_loss
+from ...config import check_augment, check_bone_loss, check_clip_metrics, check_pose_augment, check_reg_loss
 from ...mel import MelSpectrogram
 from ...optim import FlatAdam
 from ..datasets.gesture_dataset import PoseTransforms
@@ -45,6 +45,16 @@ class Voice2PoseModel(nn.Module):
         # TRAIN.AUGMENT, validated; None = off: no Augmenter exists and the forward pass is the one it was
         self.aug_opts = check_augment(cfg)
         self._augmenters = {}  # device -> augment.Augmenter (tables and workspaces), built by the first training forward pass
+        # TRAIN.POSE_AUGMENT, validated; None = off: no PoseAugmenter exists, the code table has one row per clip
+        self.pose_aug_opts = check_pose_augment(cfg)
+        self._pose_augmenters = {}  # device -> pose_augment.PoseAugmenter, built by the first training forward pass
+        self.num_clips = num_train_samples  # N: a mirrored clip i trains row N + i of a (2 N)-row table
+        if self.pose_aug_opts is not None:
+            from ... import pose_augment
+            rows_of = lambda n: pose_augment.table_rows(self.pose_aug_opts, n)  # noqa: E731
+            mirrored = pose_augment.mirrors(self.pose_aug_opts)
+        else:
+            rows_of, mirrored = (lambda n: n), False
         self.mel_transfm = MelSpectrogram(win_length=400, hop_length=160, n_fft=512, f_min=55, f_max=7500.0, n_mels=80)
         self.netG = get_model(cfg.VOICE2POSE.GENERATOR.NAME)(cfg)
         code = cfg.VOICE2POSE.GENERATOR.CLIP_CODE
@@ -66,16 +76,28 @@ class Voice2PoseModel(nn.Module):
                     ckpt = torch.load(path, map_location='cpu')
                     self.clips_code = {k.replace('module.', ''): v for k, v in ckpt['model_state_dict'].items()
                                        if 'clip_code' in k}['clip_code_mu']
-                if num_train_samples is not None and self.clips_code.shape[0] < num_train_samples:
+                if num_train_samples is not None and self.clips_code.shape[0] < rows_of(num_train_samples):
                     # the reference leaves this shape check commented out and fails later with an IndexError on the first
                     # clip beyond the table; fail here, before any kernel sees such an index
+                    if mirrored:
+                        raise RuntimeError('external clip codes have %d rows but the training set has %d clips and TRAIN.POSE_AUGMENT.MIRROR_PROB '
+                                           '> 0 needs %d (a mirrored clip i reads row %d + i: take the codes of a pose2pose run with the '
+                                           'mirror on)' % (self.clips_code.shape[0], num_train_samples, rows_of(num_train_samples),
+                                                           num_train_samples))
                     raise RuntimeError('external clip codes have %d rows but the training set has %d clips'
                                        % (self.clips_code.shape[0], num_train_samples))
             else:
                 if num_train_samples is None:
                     assert state_dict is not None, 'No state_dict available, while no dataset is configured.'
-                    num_train_samples = state_dict['module.clips_code'].shape[0]
-                self.clips_code = nn.Parameter(torch.zeros(num_train_samples, code.DIMENSION), requires_grad=code.TRAIN)
+                    rows = state_dict['module.clips_code'].shape[0]
+                    self.num_clips = rows // 2 if mirrored else rows
+                else:
+                    rows = rows_of(num_train_samples)
+                    saved = None if state_dict is None else state_dict.get('module.clips_code', state_dict.get('clips_code'))
+                    if saved is not None and (mirrored or saved.shape[0] == 2 * num_train_samples):
+                        from ... import pose_augment
+                        pose_augment.check_table_rows('the checkpoint\'s clips_code', saved.shape[0], self.pose_aug_opts, num_train_samples)
+                self.clips_code = nn.Parameter(torch.zeros(rows, code.DIMENSION), requires_grad=code.TRAIN)
         else:
             self.clips_code = None
         if cfg.VOICE2POSE.POSE_ENCODER.NAME is not None:
@@ -113,6 +135,14 @@ class Voice2PoseModel(nn.Module):
             self._augmenters[key] = Augmenter(self.aug_opts, dev)
         return self._augmenters[key]
 
+    def _pose_augmenter(self, dev):
+        key = str(dev)
+        if key not in self._pose_augmenters:
+            from ...pose_augment import PoseAugmenter
+            assert self.num_clips is not None, 'TRAIN.POSE_AUGMENT needs the number of training clips'
+            self._pose_augmenters[key] = PoseAugmenter(self.pose_aug_opts, dev, self.num_clips)
+        return self._pose_augmenters[key]
+
     def _eval_code(self, batch, n, dev, poses_gt, dataset, speaker, interpolation_coeff, return_loss):
         """Code selection outside training (voice2pose.py:95-120)."""
         code = self.cfg.VOICE2POSE.GENERATOR.CLIP_CODE
@@ -133,7 +163,10 @@ class Voice2PoseModel(nn.Module):
                 cb = table[torch.full((n,), self.cfg.DEMO.CODE_INDEX_B, dtype=torch.long, device=dev)]
                 c = c * (1 - interpolation_coeff) + cb * interpolation_coeff
             return c
-        return table[torch.randint(table.size(0), (n,), device=dev)]
+        # (with TRAIN.POSE_AUGMENT.MIRROR_PROB > 0 rows N .. 2 N - 1 hold the mirrored clips' codes: the random rows stay those of the clips
+        # as they are, so validation numbers compare with a run without the key; the default draws from the whole table as it always did)
+        rows = self.num_clips if self.pose_aug_opts is not None and self.num_clips is not None else table.size(0)
+        return table[torch.randint(min(rows, table.size(0)), (n,), device=dev)]
 
     def forward(self, batch, dataset, return_loss=True, interpolation_coeff=None, condition_code=None):
         """``condition_code`` (n, D): outside training, the codes to condition on in place of ``_eval_code``'s choice (the long-form demo keeps
@@ -146,11 +179,19 @@ class Voice2PoseModel(nn.Module):
         clip_indices = batch['clip_index'].to(dev, non_blocking=True)
         num_frames = int(batch['num_frames'][0])
         poses_gt = batch['poses'].to(dev, non_blocking=True) if return_loss else None
+        poses_score = None  # (read from the batch where a loss asks for it; the augmented confidences under TRAIN.POSE_AUGMENT)
+        if self.training and return_loss and self.pose_aug_opts is not None:  # before anything reads the poses or the clip indices' rows
+            from ...pose_augment import batch_poses
+            want_score = (self.reg_opts is not None and self.reg_opts[1] is not None) or \
+                         (self.bone_opts is not None and self.bone_opts[3] is not None)
+            poses_gt, poses_score, code_rows = batch_poses(self._pose_augmenter(dev), batch, dev, want_score)
+        else:
+            code_rows = clip_indices
 
         kl = kl_valid = None
         if g.CLIP_CODE.DIMENSION is not None:
             if self.training:
-                condition_code, kl, kl_valid = ops.CodeGatherKLFn.apply(self._code_table(dev), clip_indices, g.LAMBDA_CLIP_KL)
+                condition_code, kl, kl_valid = ops.CodeGatherKLFn.apply(self._code_table(dev), code_rows, g.LAMBDA_CLIP_KL)
             else:
                 if condition_code is None:
                     condition_code = self._eval_code(batch, audio.shape[0], dev, poses_gt, dataset, speaker, interpolation_coeff,
@@ -184,7 +225,7 @@ class Voice2PoseModel(nn.Module):
             g_loss = reg
         else:  # masked / part-weighted L1 and the velocity term in one fused op
             lam_vel, min_conf, _ = self.reg_opts
-            score = batch['poses_score'].to(dev, non_blocking=True) if min_conf is not None else None
+            score = (batch['poses_score'].to(dev, non_blocking=True) if poses_score is None else poses_score) if min_conf is not None else None
             reg, vel = ops.RegLossFn.apply(poses_pred, poses_gt, score, self._chan_weights(dev), float(g.LAMBDA_REG), lam_vel, min_conf)
             losses['G_reg_loss'] = reg
             g_loss = reg
@@ -194,7 +235,7 @@ class Voice2PoseModel(nn.Module):
         if self.bone_opts is not None:  # limb length / limb direction on the de-normalised global keypoints, one fused op (section 29)
             lam_bone, lam_dir, min_len, min_conf, _ = self.bone_opts
             stat = batch['speaker_stat']
-            score = batch['poses_score'].to(dev, non_blocking=True) if min_conf is not None else None
+            score = (batch['poses_score'].to(dev, non_blocking=True) if poses_score is None else poses_score) if min_conf is not None else None
             bone, bone_dir = ops.BoneLossFn.apply(poses_pred, poses_gt, stat['mean'].to(dev, non_blocking=True),
                                                   stat['std'].to(dev, non_blocking=True), score, self.bone_table, lam_bone, lam_dir,
                                                   min_conf, min_len)
@@ -390,7 +431,8 @@ class Voice2Pose(Trainer):
         # SYS.HIP_GRAPH: replay the captured step (forward, metrics, backward, gradient exchange, Adam): the host copies the batch into the graph's
         # static inputs and launches ONE graph instead of ~270 kernels -- on one GPU and under data parallelism alike (graph.GraphedStep captures the
         # RCCL all-reduces with the step, or replays two graphs around an eager exchange; steps that save results run eagerly: they need the final poses)
-        if self.model.aug_opts is not None:  # TRAIN.AUGMENT: the step is an input of the batch, so a replayed graph follows it
+        if self.model.aug_opts is not None or self.model.pose_aug_opts is not None:  # TRAIN.AUGMENT / TRAIN.POSE_AUGMENT: the step is an
+            # input of the batch, so a replayed graph follows it
             batch = dict(batch, aug_step=torch.tensor([global_step], dtype=torch.int64))
         losses, results = self.graphed_or_eager_step(batch, eager_ok=not save_step, want_final=bool(save_step))
         self.write_histograms(global_step)  # (SYS.HISTOGRAM_INTERVAL: after the step, outside the captured graph)

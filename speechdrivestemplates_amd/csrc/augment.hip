@@ -11,6 +11,7 @@
 //   over the chunks  lane l of one wave adds the partials l, l + 64, l + 128, .. in that order from +0.0, then the same butterfly.
 // Every float64 multiply, add and divide goes through sdt_exact::*_rn (no FMA); every square is exact in float64.  No atomics.
 #include "exact_lanes.h"
+#include "philox.h"
 
 using namespace sdt_exact;
 
@@ -22,29 +23,9 @@ constexpr int kMaxMasks = 4;
 constexpr int64_t kMaxL = (int64_t)1 << 24;
 constexpr double kNoiseScale = 0x1.bb67ae86627e7p-16;  // 1 / sqrt(4 (65536^2 - 1) / 12): unit variance of the centred sum of four 16-bit halves
 
-struct Key {
-    uint32_t k0, k1;
-};
-struct Words {
-    uint32_t w[4];
-};
-
-// Philox4x32-10 (Salmon et al., Random123): counter (c0, c1, c2, c3), key (k0, k1)
-__device__ __forceinline__ Words philox4x32(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, Key key) {
-    uint32_t k0 = key.k0, k1 = key.k1;
-#pragma unroll
-    for (int r = 0; r < 10; ++r) {
-        const uint32_t hi0 = __umulhi(0xD2511F53u, c0), lo0 = 0xD2511F53u * c0;
-        const uint32_t hi1 = __umulhi(0xCD9E8D57u, c2), lo1 = 0xCD9E8D57u * c2;
-        c0 = hi1 ^ c1 ^ k0;
-        c1 = lo1;
-        c2 = hi0 ^ c3 ^ k1;
-        c3 = lo0;
-        k0 += 0x9E3779B9u;
-        k1 += 0xBB67AE85u;
-    }
-    return {{c0, c1, c2, c3}};
-}
+using sdt_philox::Key;  // Philox4x32-10 lives in philox.h, shared with pose_augment.hip
+using sdt_philox::Words;
+using sdt_philox::philox4x32;
 
 // one workgroup of 256 threads per (chunk, clip): the chunk's partial sum of squares
 __global__ __launch_bounds__(256) void aug_sumsq_chunk_kernel(const float* __restrict__ x, int L, int n_chunks, double* __restrict__ partials) {
