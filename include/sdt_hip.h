@@ -1100,6 +1100,46 @@ int sdt_pose_augment_f32(const float* poses, const float* score_or_null, const d
                          const int32_t* perm, const double* scale_table, const double* rot_table, float* poses_out, float* score_out,
                          int64_t* eff_index, void* rec, void* stream);
 
+/*
+ * Motion histograms and Hellinger distances at validation (TEST.MOTION_DIST; speechdrivestemplates_amd/motion_dist.py; DESIGN.md section 31
+ * is the contract, motion_dist.motion_dist_model / epoch_model are the same operations in numpy; no counterpart in the reference).  pred / gt:
+ * (R, T, 2, K) float64, parts: K bytes in {0, 1, 2} (body, face, hands); part index p = 0 is "all", p = 1 + byte; source s = 0 is the
+ * prediction, 1 the ground truth; order o = 0, 1, 2 is speed, acceleration, jerk.  Differences are successive, each subtraction rounded on its
+ * own: d1(t) = x(t+1) - x(t), d2(t) = d1(t+1) - d1(t), d3(t) = d2(t+1) - d2(t), per coordinate; order o has T - 1 - o terms per keypoint.
+ * q = dx * dx + dy * dy, every operation rounded on its own (csrc/exact_f64.h); no floating-point atomics, no allocation, no host
+ * synchronisation; every pointer except ``tables`` (a host array, read during the call) is a device buffer; every size is checked before the
+ * launch (K in [1, 128], T in [1, 65536], m in [1, 16], m * T * K < 2^31; otherwise SDT_ERR_ARG).
+ *   edges: (3, 2, 31) float64: per order the 31 ascending inner edges (> 0, finite), then their squares e * e as the host rounded them.  The
+ *     bin of a term is the number of squared edges <= q (0 .. 31): a q equal to a squared edge belongs to the upper bin, +inf to bin 31; a NaN
+ *     is counted nowhere and sets nonfinite.
+ *   A record is SDT_MOTION_DIST_COLS = 316 words of 8 bytes: float64 [0,24) mag_sum[12 s + 4 o + p], the sum of sqrt(q); [24,312) the 576
+ *     counts as int32 pairs: count i = ((3 s + o) * 3 + part) * 32 + bin (part 0 body, 1 face, 2 hands) sits in word 24 + i / 2, in the low 32
+ *     bits for an even i and the high 32 bits for an odd one; int64 312 seen, 313 copies, 314 nonfinite (a NaN term, or a float sum that is
+ *     not finite), 315 frames.
+ *   rows: one record per row (seen 1, copies 1) into rows (R x 316 words).  One workgroup of four waves per row, two per source, lane k of a
+ *     pair holds keypoint k; within a frame the lanes' sqrt terms (+0.0 outside the part) go through the xor butterfly 32, 16, 8, 4, 2, 1
+ *     inside each wave, then wave 0 + wave 1; the frame sums of an order are added in frame order from +0.0.
+ *   commit: the m row records of clip b (rows j * B + b) added in order j = 0..m-1 into row clip_index[b] of table, (N + 1) x 316 words: row
+ *     N is the header, whose word 0 counts the indices outside [0, N) (they write nothing else).
+ *   epoch: tables are ranks (1..64) table pointers; clip n takes the record of the lowest rank with seen set, records with nonfinite set are
+ *     left out and counted.  Counts are summed exactly, float sums in chunks of 64 clips in index order, then the chunk partials in order;
+ *     "all" is the sum of the three parts.  work: sdt_motion_dist_epoch_work_words(N) = ceil(N / 64) * 896 words.  For counts a_b, b_b with
+ *     totals na, nb: BC = sum over b in order from +0.0 of sqrt((a_b / na) * (b_b / nb)), H = sqrt(max(1 - BC, +0.0)); both 0.0 if na or nb
+ *     is 0.  out (SDT_MOTION_DIST_OUT_COLS = 64 words), index r = 4 o + p: float64 [0,12) H[r] and [12,24) BC[r] of the prediction against
+ *     the ground truth, [24,36) H_floor[r] and [36,48) BC_floor[r] of the ground truth of the clips with an even index against that of the
+ *     clips with an odd index, [48,60) ratio[r] = sum mag_sum_pred / sum mag_sum_gt (0.0 for a divisor of 0); int64 60 clips with a record,
+ *     61 of them left out as nonfinite, 62 index errors of all tables, 63 zero.  hist: (2, 3, 4, 32) int64, the merged histograms
+ *     [s][o][p][bin] with "all" filled in.
+ *   The square root is the one sdt_clip_metrics_sqrt_f64 probes.
+ */
+#define SDT_MOTION_DIST_COLS 316
+#define SDT_MOTION_DIST_OUT_COLS 64
+int sdt_motion_dist_rows_f64(const double* pred, const double* gt, const uint8_t* parts, const double* edges, int R, int T, int K, void* rows,
+                             void* stream);
+int sdt_motion_dist_commit(const void* rows, const int64_t* clip_index, int B, int m, int T, int K, void* table, int64_t N, void* stream);
+int64_t sdt_motion_dist_epoch_work_words(int64_t N);
+int sdt_motion_dist_epoch(const void* const* tables, int ranks, int64_t N, void* work, void* out, void* hist, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

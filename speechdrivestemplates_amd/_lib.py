@@ -214,6 +214,10 @@ SIGNATURES = {
     "sdt_augment_audio_f32": [_p, _i, _i64, _p, _p, _p, C.c_uint64, _i64, _i64, _i, _p, _p, _p, _p, _p],
     "sdt_augment_mel_mask_f32": [_p, _i, _i, _i, _p, _p, C.c_uint64, _i, _i, _i, _i, _p, _p],
     "sdt_pose_augment_f32": [_p, _p, _p, _p, _i, _i, _i, _p, _p, _i64, C.c_uint64, _i64, _i, C.POINTER(C.c_int32), _p, _p, _p, _p, _p, _p, _p],
+    "sdt_motion_dist_rows_f64": [_p, _p, _p, _p, _i, _i, _i, _p, _p],
+    "sdt_motion_dist_commit": [_p, _p, _i, _i, _i, _i, _p, _i64, _p],
+    "sdt_motion_dist_epoch_work_words": [_i64],  # (returns int64_t: restype set in load())
+    "sdt_motion_dist_epoch": [C.POINTER(C.c_void_p), _i, _i64, _p, _p, _p, _p],
 }
 F32, BF16 = 0, 1  # enum sdt_dtype
 
@@ -279,6 +283,7 @@ def load():
     lib.sdt_sync_onset_capacity.restype = C.c_int64
     lib.sdt_sync_workspace_bytes.restype = C.c_int64
     lib.sdt_augment_workspace_bytes.restype = C.c_int64
+    lib.sdt_motion_dist_epoch_work_words.restype = C.c_int64
     for name in ("threads", "chunk", "buckets", "max_segments"):
         getattr(lib, "sdt_tensor_hist_" + name).restype = C.c_int64
     lib.sdt_conv_dw_group_plan_bytes.argtypes = [_i]

@@ -1,10 +1,10 @@
-"""The record-table protocol of the per-clip validation metrics, shared by clip_metrics and sync_metrics (DESIGN.md section 22 states it;
+"""The record-table protocol of the per-clip validation metrics, shared by clip_metrics, sync_metrics and motion_dist (DESIGN.md section 22 states it;
 csrc/record_table.h is the device side).
 
 A table is a (num_clips + 1, cols) int64 tensor: one record per clip of the validation set, then a header row whose word 0 counts the clip
 indices outside the table.  Under data parallelism there is one table per rank; per clip the lowest rank whose record has its seen word set
 gives the record.  The epoch sum runs over chunks of 64 clips in index order, then over the chunk partials in order.  The word layouts, what
-each word adds up and the final divisions belong to the two families."""
+each word adds up and the final divisions belong to the families."""
 import numpy as np
 
 from ._exact_model import MAX_TABLES

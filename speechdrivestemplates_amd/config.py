@@ -107,7 +107,17 @@ _DEFAULTS = {
              # results/epoch<E>-<TAG>-sync_metrics.npz.  With DEMO.LONG_FORM the long demo reports the same counts over the whole recording.
              # SYNC_TOLERANCE: a beat within this many seconds of an onset is a hit (floor(300 tol + 0.5) ticks of 1/300 s, 1 .. 150).
              # SYNC_SIGMA: the width in seconds of the Gaussian that beat_align weighs a beat's distance with.  False = the loop as it was.
-             "SYNC_METRICS": False, "SYNC_TOLERANCE": 0.1, "SYNC_SIGMA": 0.1},
+             "SYNC_METRICS": False, "SYNC_TOLERANCE": 0.1, "SYNC_SIGMA": 0.1,
+             # extensions (motion histograms, motion_dist.MotionDistAccumulator / csrc/motion_dist.hip; Voice2Pose only).
+             # MOTION_DIST True = every test_step also commits, per clip, the 32-bin histograms of speed, acceleration and jerk magnitudes
+             # of the prediction and the ground truth per body part to a table on the GPU, and validate() / test() add hellinger_speed /
+             # _accel / _jerk (each also _hands, and _floor = the same distance between two halves of the ground truth), accel_ratio,
+             # jerk_ratio (each also _hands) and motion_clips_nonfinite to their values: over the tables of ALL ranks, the same bits on every
+             # rank.  With SAVE_NPZ the master also writes results/epoch<E>-<TAG>-motion_metrics.npz (the table, the edges, the merged
+             # histograms); with SYS.TENSORBOARD the merged histograms as <val|test>/motion/<speed|accel|jerk>_<pred|gt>_<part>.  False = the
+             # loop as it was.  MOTION_DIST_EDGES: None = 2 ** ((j - 15) / 3), j = 0 .. 30, final-pose pixels per frame^o for every order
+             # (untuned), else three lists (speed, accel, jerk) of 31 ascending numbers > 0.
+             "MOTION_DIST": False, "MOTION_DIST_EDGES": None},
     "DEMO": {"MULTIPLE": 1, "NUM_SAMPLES": 1, "CODE_INDEX": None, "CODE_INDEX_B": None, "CODE_PATH": None,
              # extensions (the whole-recording demo, long_demo.LongDemo / csrc/long_demo.hip; Voice2Pose only).
              # LONG_FORM True = a demo input of F >= DATASET.NUM_FRAMES frames is generated as overlapping windows of NUM_FRAMES frames (the
@@ -342,6 +352,32 @@ def check_sync_metrics(cfg):
     if isinstance(m, bool) or not isinstance(m, int) or not 1 <= m <= 16:
         raise ValueError("TEST.SYNC_METRICS takes TEST.MULTIPLE from 1 to 16, got %r" % (m,))
     return {'tol_ticks': ticks, 'sigma': float(sigma)}
+
+
+def check_motion_dist(cfg):
+    """Validate TEST.MOTION_DIST / TEST.MOTION_DIST_EDGES (ValueError names the key; the edges are checked whether or not the key is on).
+    Returns None with the key off, else {'edges': None for the default ladder, or three tuples of 31 Python floats}."""
+    on, edges = cfg.TEST.MOTION_DIST, cfg.TEST.MOTION_DIST_EDGES
+    if not isinstance(on, bool):
+        raise ValueError("TEST.MOTION_DIST must be True or False, got %r" % (on,))
+    if edges is not None:
+        if not isinstance(edges, (list, tuple)) or len(edges) != 3 or not all(isinstance(r, (list, tuple)) and len(r) == 31 for r in edges):
+            raise ValueError("TEST.MOTION_DIST_EDGES must be None or three lists (speed, accel, jerk) of 31 numbers, got %r" % (edges,))
+        for row in edges:
+            if not all(_is_number(e) and e > 0 and _is_number(float(e) * float(e)) and float(e) * float(e) > 0 for e in row):
+                raise ValueError("TEST.MOTION_DIST_EDGES: every edge must be a finite number > 0 (and so must its square), got %r" % (row,))
+            if not all(a < b for a, b in zip(row[:-1], row[1:])):
+                raise ValueError("TEST.MOTION_DIST_EDGES: the edges of every order must be strictly ascending, got %r" % (row,))
+        edges = tuple(tuple(float(e) for e in row) for row in edges)
+    if not on:
+        return None
+    if cfg.PIPELINE_TYPE != "Voice2Pose":
+        raise ValueError("TEST.MOTION_DIST is a Voice2Pose key (motion histograms of predicted gestures against the ground truth), got "
+                         "PIPELINE_TYPE %r" % (cfg.PIPELINE_TYPE,))
+    m = cfg.TEST.MULTIPLE
+    if isinstance(m, bool) or not isinstance(m, int) or not 1 <= m <= 16:
+        raise ValueError("TEST.MOTION_DIST takes TEST.MULTIPLE from 1 to 16, got %r" % (m,))
+    return {'edges': edges}
 
 
 def check_augment(cfg):

@@ -41,10 +41,11 @@ class Trainer(object):
         if not torch.cuda.is_available():
             raise RuntimeError('this engine needs an AMD GPU (no CPU fallback); torch.cuda.is_available() is False')
         torch.cuda.set_device(int(os.environ.get('LOCAL_RANK', self.get_rank() % max(1, torch.cuda.device_count()))))
-        from ...config import check_augment, check_clip_metrics, check_histograms, check_long_demo, check_sync_metrics
+        from ...config import check_augment, check_clip_metrics, check_histograms, check_long_demo, check_motion_dist, check_sync_metrics
         check_histograms(cfg)  # SYS.HISTOGRAM_INTERVAL without SYS.TENSORBOARD: there is nowhere to write
         check_clip_metrics(cfg)  # TEST.CLIP_METRICS / TEST.PCK_ALPHAS (a Voice2Pose key)
         check_sync_metrics(cfg)  # TEST.SYNC_METRICS / SYNC_TOLERANCE / SYNC_SIGMA (a Voice2Pose key)
+        check_motion_dist(cfg)  # TEST.MOTION_DIST / MOTION_DIST_EDGES (a Voice2Pose key)
         check_long_demo(cfg)  # DEMO.LONG_FORM and its window / smoothing / segment keys (a Voice2Pose key)
         check_augment(cfg)  # TRAIN.AUGMENT: audio augmentation inside the train step (a Voice2Pose key)
 
@@ -492,6 +493,10 @@ class Trainer(object):
         """TEST.SYNC_METRICS and a pipeline that has speech-gesture synchrony metrics (Voice2Pose)"""
         return False
 
+    def uses_motion_dist(self):
+        """TEST.MOTION_DIST and a pipeline that has motion histograms (Voice2Pose)"""
+        return False
+
     # -- loops (trainer.py:367-427) ----------------------------------------------------------------------
     def train(self, cfg, exp_tag, resume_from=None):
         """``pipeline.train(cfg, exp_tag, args.resume_from)`` as main.py:51 calls it (trainer.py:367).  ``cfg`` is the object
@@ -551,6 +556,9 @@ class Trainer(object):
         sync_metrics = self.uses_sync_metrics()
         if sync_metrics and self.sync_metrics() is not None:
             self.sync_metrics().reset()
+        motion_dist = self.uses_motion_dist()
+        if motion_dist and self.motion_dist() is not None:
+            self.motion_dist().reset()
         for t_step, batch in enumerate(test_dataloader):
             losses, res = self.test_step(batch, t_step + 1, epoch)
             for k, v in losses.items():
@@ -567,6 +575,8 @@ class Trainer(object):
             out.update(self.evaluate_clip_metrics(epoch, tag))
         if sync_metrics:  # likewise: one all-gather of the synchrony tables
             out.update(self.evaluate_sync_metrics(epoch, tag))
+        if motion_dist:  # likewise: one all-gather of the motion-histogram tables
+            out.update(self.evaluate_motion_dist(epoch, tag))
         if self.is_master_process():
             logging.info('[VAL] epoch: %d  val_time: %.1f min  ' % (epoch, (time.time() - tic) / 60) +
                          ''.join('%s: %.5f  ' % (k, float(v)) for k, v in out.items()))

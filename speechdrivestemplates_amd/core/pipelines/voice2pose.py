@@ -472,6 +472,8 @@ class Voice2Pose(Trainer):
             self.clip_metrics(fin_p).add(fin_p, fin_g, batch['clip_index'], m)
         if self.uses_sync_metrics():  # TEST.SYNC_METRICS: audio onsets against the beats of both pose tensors, all on the device
             self.sync_metrics(fin_p).add(fin_p, fin_g, batch['audio'].to(dev, non_blocking=True).float(), batch['clip_index'], m)
+        if self.uses_motion_dist():  # TEST.MOTION_DIST: the clips' speed / acceleration / jerk histograms go into the table on the device
+            self.motion_dist(fin_p).add(fin_p, fin_g, batch['clip_index'], m)
         if self.cfg.SYS.DISTRIBUTED:
             dp.reduce_scalars(losses)
         if self.is_master_process():
@@ -597,7 +599,7 @@ class Voice2Pose(Trainer):
         return self._evaluate_record_table(self.clip_metrics(), clip_metrics, 'clip', '', epoch, tag, lambda acc: (acc.alphas,))
 
     def _evaluate_record_table(self, acc, module, label, prefix, epoch, tag, save_args):
-        """the epoch values of one record table (``module``: clip_metrics or sync_metrics): all-gather the ranks' states, ``result``, warn
+        """the epoch values of one record table (``module``: clip_metrics, sync_metrics or motion_dist): all-gather the ranks' states, ``result``, warn
         about clips left out, save the merged table with TEST.SAVE_NPZ (``save_args(acc)``: what ``module.save_table`` takes after the
         records) and drop the bookkeeping entries"""
         if acc is None:  # no validation step ran
@@ -638,6 +640,39 @@ class Voice2Pose(Trainer):
         ``evaluate_clip_metrics`` merges its tables.  A clip with a non-finite sum is left out, counted and warned about."""
         from ... import sync_metrics
         return self._evaluate_record_table(self.sync_metrics(), sync_metrics, 'sync', 'sync_', epoch, tag, lambda acc: (acc.tol, acc.sigma))
+
+    def uses_motion_dist(self):
+        return bool(getattr(self.cfg.TEST, 'MOTION_DIST', False))
+
+    def motion_dist(self, poses=None):
+        """the table of motion-histogram records (created at the first step, which knows the keypoint count and the device); one row per clip
+        of the validation set, addressed by the batch's 'clip_index'"""
+        if getattr(self, '_motion_dist', None) is None and poses is not None:
+            from ...config import check_motion_dist
+            from ...motion_dist import MotionDistAccumulator
+            ds = getattr(self.test_dataset, 'dataset', self.test_dataset)  # (a Subset keeps the indices of the set it was cut from)
+            self._motion_dist = MotionDistAccumulator(len(ds), poses.shape[3], check_motion_dist(self.cfg)['edges'], poses.device,
+                                                      parts=PoseTransforms.part_table())
+        return getattr(self, '_motion_dist', None)
+
+    def evaluate_motion_dist(self, epoch, tag):
+        """Hellinger distances of the speed, acceleration and jerk histograms (prediction against ground truth, and the noise floor between
+        two halves of the ground truth) and the magnitude ratios over the clips every rank delivered, merged as ``evaluate_clip_metrics``
+        merges its tables.  A clip with a NaN term or a non-finite sum is left out, counted and warned about.  With SYS.TENSORBOARD the
+        master also writes the merged histograms."""
+        from ... import motion_dist
+        acc = self.motion_dist()
+        out = self._evaluate_record_table(acc, motion_dist, 'motion', 'motion_', epoch, tag, lambda a: (a.edges, a.histograms()))
+        tb = getattr(self, 'tb_writer', None)
+        if acc is not None and tb is not None and self.is_master_process():
+            hist = acc.histograms()  # (the merged histograms of the result() above)
+            for s, source in enumerate(motion_dist.SOURCES):
+                for o, order in enumerate(motion_dist.ORDERS):
+                    for p, part in enumerate(motion_dist.PARTS):
+                        tb.add_histogram_raw('%s/motion/%s_%s_%s' % (tag.lower(), order, source, part),
+                                             *motion_dist.tb_histogram_fields(hist[s, o, p], acc.edges[o]), step=epoch)
+            tb.flush()
+        return out
 
     def evaluate_epoch(self, results_dict):
         from ...fgd import compute_fgd

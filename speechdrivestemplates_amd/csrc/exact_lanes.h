@@ -1,4 +1,4 @@
-// The lane helpers of the bit-exact metric kernels, shared by clip_metrics.hip, sync_metrics.hip, long_demo.hip and augment.hip: these are the
+// The lane helpers of the bit-exact metric kernels, shared by clip_metrics.hip, sync_metrics.hip, long_demo.hip, augment.hip and motion_dist.hip: these are the
 // summation order of their contracts (_exact_model.py holds the same operations in numpy).
 #pragma once
 #include "exact_f64.h"

@@ -1,8 +1,8 @@
-// The record-table protocol of the per-clip validation metrics, shared by clip_metrics.hip and sync_metrics.hip (DESIGN.md section 22 states it;
+// The record-table protocol of the per-clip validation metrics, shared by clip_metrics.hip, sync_metrics.hip and motion_dist.hip (DESIGN.md section 22 states it;
 // _record_table.py is the host side).  A table is (N + 1, cols) int64: one record per clip of the validation set, then a header row whose
 // word 0 counts the clip indices outside the table.  Under data parallelism there is one table per rank, and per clip the lowest rank whose
 // record has its seen word set gives the record.  The epoch sum runs over chunks of 64 clips in index order, then over the chunk partials in
-// order.  The word layouts, what each word adds up and the final divisions belong to the two families.
+// order.  The word layouts, what each word adds up and the final divisions belong to the families.
 #pragma once
 #include "exact_lanes.h"
 
