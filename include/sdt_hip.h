@@ -346,7 +346,8 @@ typedef struct sdt_chain1d_layer {
     float* dy;              /* (B, To, 256) backward: gradient of y (the weight gradient's other operand) */
     float* dx;              /* (B, Ti, Cin) backward: gradient of the conv's input */
 } sdt_chain1d_layer;
-/* 1 when every block maps to a built K loop and the current device can hold a window of clusters, else 0. */
+/* 1 when every block maps to a built K loop, every block but the last has a consumer (at most two direct ones and one upsampling one) and the
+ * current device can hold a window of clusters, else 0.  The forward and the backward entry refuse (SDT_ERR_ARG, no launch) exactly what this refuses. */
 int sdt_chain1d_supported(const sdt_chain1d_layer* layers, int nlayers, int B);
 /* zout (B, To_last, 256) = act(norm(y[nlayers-1])).  counters: >= min(B, 8 * (CUs / 64)) zero-initialised uint32 (zero again when a launch ends); err: one uint32
  * that a launch sets non-zero when a workgroup gave up waiting for its cluster (sdt_convsk_set_spin_limit) -- results are then invalid. */

@@ -739,7 +739,7 @@ static int chain_check(const sdt_chain1d_layer* Ls, int n, int B, bool pointers 
         SDT_CHECK_ARG(L.Ti >= 1 && L.Ti <= CH_MAXT && L.To >= 1 && L.To <= CH_MAXT, "frames per clip out of range (1..64)");
         SDT_CHECK_ARG(L.Cin % 32 == 0 && L.Cin >= 32 && L.Cin <= CH_MAXCIN, "input channels must be a multiple of 32, at most 320");
         SDT_CHECK_ARG(L.k >= 1 && L.k <= 8 && L.stride >= 1 && L.stride <= 2 && L.pad >= 0 && L.pad < L.k, "kernel / stride / padding out of range");
-        SDT_CHECK_ARG(L.To == (L.Ti + 2 * L.pad - L.k) / L.stride + 1, "output length does not match the geometry");
+        SDT_CHECK_ARG(L.Ti + 2 * L.pad >= L.k && L.To == (L.Ti + 2 * L.pad - L.k) / L.stride + 1, "output length does not match the geometry");
         SDT_CHECK_ARG(L.pad + L.Ti + std::max(0, (L.To - 1) * L.stride + L.k - 1 - L.pad - (L.Ti - 1)) <= CH_ROWS, "padded input exceeds the LDS tile");
         SDT_CHECK_ARG(L.in_mode >= 0 && L.in_mode <= 2, "unknown input mode");
         SDT_CHECK_ARG((L.in_mode == 0) == (l == 0), "exactly block 0 reads the external input");
@@ -756,6 +756,20 @@ static int chain_check(const sdt_chain1d_layer* Ls, int n, int B, bool pointers 
         SDT_CHECK_ARG(chain_variant((KC / (L.To > 32 ? 2 : 4)) >> 3, L.k * L.Cin / KC) && chain_variant((128 / (L.Ti > 32 ? 2 : 4)) >> 3, 2 * L.k),
                       "no K loop was built for this block (kernel size 3 or 4; 256 or 288 input channels)");
         SDT_CHECK_ARG(!pointers || (L.w != nullptr && L.y != nullptr), "NULL weight / output");
+    }
+    // the consumer tables the backward launch gathers a block's output gradient from (chain_fill): two direct consumers (g_id0, g_id1) and one
+    // upsampling consumer (g_up) per block, and no block but the last without any -- refused HERE, so that sdt_chain1d_supported and the forward
+    // entry say what the backward entry will say
+    int direct[CH_MAXL] = {0}, up[CH_MAXL] = {0};
+    for (int m = 1; m < n; ++m) {
+        const sdt_chain1d_layer& L = Ls[m];
+        ++direct[L.in_mode == 1 ? L.src_a : L.src_b];
+        if (L.in_mode == 2) ++up[L.src_a];
+    }
+    for (int l = 0; l < n; ++l) {
+        SDT_CHECK_ARG(direct[l] <= 2, "more than two direct consumers of one block");
+        SDT_CHECK_ARG(up[l] <= 1, "more than one upsampling consumer of one block");
+        SDT_CHECK_ARG(l == n - 1 || direct[l] + up[l] > 0, "a block without consumers");
     }
     return SDT_OK;
 }
@@ -783,29 +797,17 @@ static int chain_fill(ch_args& A, const sdt_chain1d_layer* Ls, int n, int B, flo
         L.w = S.w, L.wt = S.wt, L.y = S.y, L.x = S.x, L.dy = S.dy, L.dx = S.dx;
     }
     if (bwd) {
-        // consumers of every block's output, from the forward wiring; the last block's output gradient is external
+        // consumers of every block's output, from the forward wiring (chain_check() has bounded their number); the last block's output
+        // gradient is external
         A.L[n - 1].g_id0 = n;
         for (int m = 1; m < n; ++m) {
             const sdt_chain1d_layer& S = Ls[m];
-            auto add_id = [&](int src) {
-                ch_layer& P = A.L[src];
-                if (P.g_id0 < 0) P.g_id0 = m;
-                else if (P.g_id1 < 0) P.g_id1 = m;
-                else return false;
-                return true;
-            };
-            if (S.in_mode == 1) SDT_CHECK_ARG(add_id(S.src_a), "more than two direct consumers of one block");
-            if (S.in_mode == 2) {
-                SDT_CHECK_ARG(add_id(S.src_b), "more than two direct consumers of one block");
-                SDT_CHECK_ARG(A.L[S.src_a].g_up < 0, "more than one upsampling consumer of one block");
-                A.L[S.src_a].g_up = m;
-            }
+            ch_layer& P = A.L[S.in_mode == 1 ? S.src_a : S.src_b];
+            (P.g_id0 < 0 ? P.g_id0 : P.g_id1) = m;
+            if (S.in_mode == 2) A.L[S.src_a].g_up = m;
         }
-        for (int l = 0; l < n; ++l) {
-            SDT_CHECK_ARG(A.L[l].g_id0 >= 0 || A.L[l].g_up >= 0, "a block without consumers");
-            SDT_CHECK_ARG(A.L[l].g_id0 != n || (A.L[l].g_id1 < 0 && A.L[l].g_up < 0) || l == n - 1, "bad consumer table");
+        for (int l = 0; l < n; ++l)
             SDT_CHECK_ARG(Ls[l].dy != nullptr && (l == 0 || (Ls[l].wt != nullptr && Ls[l].dx != nullptr)), "backward needs dy of every block, wt / dx of every block but the first");
-        }
     }
     return SDT_OK;
 }
