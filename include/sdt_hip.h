@@ -1141,6 +1141,41 @@ int sdt_motion_dist_commit(const void* rows, const int64_t* clip_index, int B, i
 int64_t sdt_motion_dist_epoch_work_words(int64_t N);
 int sdt_motion_dist_epoch(const void* const* tables, int ranks, int64_t N, void* work, void* out, void* hist, void* stream);
 
+/*
+ * Fitting template codes to clips with the generator held fixed (TEST.FIT_CODE; speechdrivestemplates_amd/code_fit.py; DESIGN.md section 32 is
+ * the contract, code_fit.loss_model / step_model / set_model / pick_model are the same operations in numpy; no counterpart in the reference).
+ * Everything of an iteration that is not the Conv1d chain or the head.  No floating-point atomics, no allocation, no host synchronisation;
+ * every operation is rounded on its own except the three fused multiply-adds of the Adam update, which are the ones adam_kernel is compiled
+ * to; every pointer is a device buffer; a clip reads and writes its own rows only.  Sizes are checked before the launch (SDT_ERR_ARG).
+ *   loss: pred, gt (B, n) fp32.  loss[b] = (sum |double(pred) - double(gt)|) / double(n) in float64, NaN when the sum is not finite;
+ *     dpred = sign(pred - gt) * float(1.0 / double(n)), sign(0) = 0, a NaN difference gives NaN.  One workgroup of 256 threads per clip:
+ *     thread t adds the elements t, t + 256, ... in that order from +0.0; wave butterfly xor 32, 16, 8, 4, 2, 1; (w0 + w1) + (w2 + w3).
+ *   step (mode 0), one wave per clip, D <= 256, in this order:
+ *     1. loss[b] < best_loss[b] (never for a NaN): best_code[b] = code[b] -- the code that produced this loss -- and best_loss[b] = loss[b];
+ *     2. g[d] = float(sum over t ascending from +0.0 of double(dh[b, t, C + d])), dh (B, T, C + D) fp32;
+ *     3. lambda > 0: g[d] = float(double(g[d]) + ((lambda * (double(code[d]) - mu[d])) * ivar[d]) / double(D)), mu and ivar (D) float64;
+ *     4. loss[b] and every g[d] of the clip finite: s = counter[0] + 1, bc1 = float(1 - pow(double(beta1), s)),
+ *        bc2s = float(sqrt(1 - pow(double(beta2), s))), step_size = lr_dev[0] / bc1, and per element in fp32
+ *          m = fma(m, beta1, (1 - beta1) * g);  v = fma(v, beta2, ((1 - beta2) * g) * g);
+ *          code = fma(-step_size, m / (sqrt(v) / bc2s + eps), code)
+ *        (sdt_adam_step_f32's update with weight_decay 0 and grad_scale 1, bit for bit on a buffer of a multiple of 4 elements);
+ *        otherwise code, m and v keep their bits and nonfinite[b] = 1 (int32, never cleared here);
+ *     5. h[b, t, C + d] = code[d] for every t: the chain's input buffer (B, T, C + D); its first C channels are not touched;
+ *     6. history[counter[0], b] = loss[b] where counter[0] < history_rows, history (history_rows, B) float64;
+ *     then counter[0] += 1 (a second launch on the same stream).  mode 1: 1 and 6 only, the counter stays (the loss of the last code).
+ *   set: h[b, t, C + d] = codes[b, d], codes (B, D) fp32.
+ *   pick: cand_loss (M, B) float64.  index[b] (int32) = the lowest j with the smallest finite cand_loss[j, b], -1 when the clip has none;
+ *     best[b] = that loss (NaN for -1); with cands (M, D) fp32 and code_out (B, D) both given, code_out[b] = cands[max(index[b], 0)].
+ */
+int sdt_code_fit_loss_f32(const float* pred, const float* gt, int B, int64_t n, double* loss, float* dpred, void* stream);
+int sdt_code_fit_step_f32(const float* dh, const double* loss, float* code, float* m, float* v, float* best_code, double* best_loss,
+                          int64_t* counter, const float* lr_dev, const double* mu, const double* ivar, double lambda, float beta1, float beta2,
+                          float eps, float* h, int B, int T, int C, int D, double* history, int64_t history_rows, int32_t* nonfinite, int mode,
+                          void* stream);
+int sdt_code_fit_set_f32(const float* codes, float* h, int B, int T, int C, int D, void* stream);
+int sdt_code_fit_pick_f32(const double* cand_loss, int M, int B, const float* cands, int D, int32_t* index, double* best, float* code_out,
+                          void* stream);
+
 #ifdef __cplusplus
 }
 #endif

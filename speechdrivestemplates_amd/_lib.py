@@ -218,6 +218,10 @@ SIGNATURES = {
     "sdt_motion_dist_commit": [_p, _p, _i, _i, _i, _i, _p, _i64, _p],
     "sdt_motion_dist_epoch_work_words": [_i64],  # (returns int64_t: restype set in load())
     "sdt_motion_dist_epoch": [C.POINTER(C.c_void_p), _i, _i64, _p, _p, _p, _p],
+    "sdt_code_fit_loss_f32": [_p, _p, _i, _i64, _p, _p, _p],
+    "sdt_code_fit_step_f32": [_p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, C.c_double, _f, _f, _f, _p, _i, _i, _i, _i, _p, _i64, _p, _i, _p],
+    "sdt_code_fit_set_f32": [_p, _p, _i, _i, _i, _i, _p],
+    "sdt_code_fit_pick_f32": [_p, _i, _i, _p, _i, _p, _p, _p, _p],
 }
 F32, BF16 = 0, 1  # enum sdt_dtype
 

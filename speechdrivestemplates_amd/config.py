@@ -117,7 +117,20 @@ _DEFAULTS = {
              # histograms); with SYS.TENSORBOARD the merged histograms as <val|test>/motion/<speed|accel|jerk>_<pred|gt>_<part>.  False = the
              # loop as it was.  MOTION_DIST_EDGES: None = 2 ** ((j - 15) / 3), j = 0 .. 30, final-pose pixels per frame^o for every order
              # (untuned), else three lists (speed, accel, jerk) of 31 ascending numbers > 0.
-             "MOTION_DIST": False, "MOTION_DIST_EDGES": None},
+             "MOTION_DIST": False, "MOTION_DIST_EDGES": None,
+             # extension (oracle-code validation, code_fit.CodeFitter / csrc/code_fit.hip; Voice2Pose with a code table
+             # only; needs MULTIPLE 1 and neither CLIP_CODE.SAMPLE_FROM_NORMAL nor TEST_WITH_GT_CODE).  ENABLE True = after its usual forward
+             # pass (whose numbers stay as they are) every test_step holds the generator fixed and fits, per clip, the code that explains the
+             # clip best -- STEPS Adam iterations at learning rate LR on the clip's own L1 loss, the best iterate kept -- and validate() /
+             # test() add L2_dist_fit, lip_sync_error_n_fit, G_reg_loss_fit, fit_loss_first, fit_code_z, fit_clips_nonfinite (and
+             # G_reg_loss_table with INIT 'table'; the TEST.CLIP_METRICS values again with the suffix _fit) to their values.  The audio
+             # encoder runs once per batch; an iteration is the Conv1d stage forward and backward, the head, and two kernels of code_fit.hip.
+             # INIT: the start code -- 'zero', 'mean' (the mean row of the trained table) or 'table' (per clip the best of the mean and
+             # CANDIDATES rows floor(j N / M) of the table, one forward pass each).  PRIOR L >= 0 adds L * mean_d((c - mu)^2 / var) / 2
+             # with the table's per-dimension mean and unbiased variance.  STEPS (1 .. 1000) and LR (> 0) are UNTUNED defaults: nobody has
+             # yet looked for the pair that converges fastest on a trained model.  CANDIDATES 0 .. 64.  False = the loop as it was, no
+             # kernel of the fit is launched.
+             "FIT_CODE": {"ENABLE": False, "STEPS": 100, "LR": 0.05, "INIT": "mean", "CANDIDATES": 0, "PRIOR": 0.0}},
     "DEMO": {"MULTIPLE": 1, "NUM_SAMPLES": 1, "CODE_INDEX": None, "CODE_INDEX_B": None, "CODE_PATH": None,
              # extensions (the whole-recording demo, long_demo.LongDemo / csrc/long_demo.hip; Voice2Pose only).
              # LONG_FORM True = a demo input of F >= DATASET.NUM_FRAMES frames is generated as overlapping windows of NUM_FRAMES frames (the
@@ -323,6 +336,47 @@ def check_clip_metrics(cfg):
 
 def _is_int(v):
     return isinstance(v, int) and not isinstance(v, bool)
+
+
+def check_fit_code(cfg):
+    """Validate TEST.FIT_CODE (ValueError names the key; the ranges are checked whether or not the key is on).  Returns None with ENABLE off,
+    else {'steps', 'lr', 'init', 'candidates', 'prior'} as Python values (code_fit.CodeFitter's opts)."""
+    f, pre = cfg.TEST.FIT_CODE, "TEST.FIT_CODE."
+    on, steps, lr, init, cands, prior = f.ENABLE, f.STEPS, f.LR, f.INIT, f.CANDIDATES, f.PRIOR
+    if not isinstance(on, bool):
+        raise ValueError(pre + "ENABLE must be True or False, got %r" % (on,))
+    if not _is_int(steps) or not 1 <= steps <= 1000:
+        raise ValueError(pre + "STEPS must be an integer from 1 to 1000, got %r" % (steps,))
+    if not _is_number(lr) or not lr > 0:
+        raise ValueError(pre + "LR must be a finite number > 0, got %r" % (lr,))
+    if init not in ("zero", "mean", "table"):
+        raise ValueError(pre + "INIT must be 'zero', 'mean' or 'table', got %r" % (init,))
+    if not _is_int(cands) or not 0 <= cands <= 64:
+        raise ValueError(pre + "CANDIDATES must be an integer from 0 to 64, got %r" % (cands,))
+    if init == "table" and cands < 1:
+        raise ValueError(pre + "CANDIDATES must be at least 1 with INIT 'table' (the table rows to try), got %r" % (cands,))
+    if not _is_number(prior) or not prior >= 0:
+        raise ValueError(pre + "PRIOR must be a finite number >= 0, got %r" % (prior,))
+    if not on:
+        return None
+    if cfg.PIPELINE_TYPE != "Voice2Pose":
+        raise ValueError(pre + "ENABLE is a Voice2Pose key (fitting a template code to a clip), got PIPELINE_TYPE %r" % (cfg.PIPELINE_TYPE,))
+    code = cfg.VOICE2POSE.GENERATOR.CLIP_CODE
+    if code.DIMENSION is None:
+        raise ValueError(pre + "ENABLE needs VOICE2POSE.GENERATOR.CLIP_CODE.DIMENSION: this generator takes no code")
+    if not _is_int(code.DIMENSION) or not 1 <= code.DIMENSION <= 256:
+        raise ValueError(pre + "ENABLE takes VOICE2POSE.GENERATOR.CLIP_CODE.DIMENSION from 1 to 256, got %r" % (code.DIMENSION,))
+    if cfg.VOICE2POSE.GENERATOR.NORM != "IN":
+        raise ValueError(pre + "ENABLE needs VOICE2POSE.GENERATOR.NORM 'IN' (an eval-mode BatchNorm stage has no backward pass in this "
+                         "engine), got %r" % (cfg.VOICE2POSE.GENERATOR.NORM,))
+    m = cfg.TEST.MULTIPLE
+    if isinstance(m, bool) or m != 1:
+        raise ValueError(pre + "ENABLE needs TEST.MULTIPLE 1 (one fit per clip), got %r" % (m,))
+    if code.SAMPLE_FROM_NORMAL:
+        raise ValueError(pre + "ENABLE does not go with VOICE2POSE.GENERATOR.CLIP_CODE.SAMPLE_FROM_NORMAL (the fit starts from the table)")
+    if code.TEST_WITH_GT_CODE:
+        raise ValueError(pre + "ENABLE does not go with VOICE2POSE.GENERATOR.CLIP_CODE.TEST_WITH_GT_CODE (the pose encoder supplies the codes)")
+    return {'steps': int(steps), 'lr': float(lr), 'init': init, 'candidates': int(cands), 'prior': float(prior)}
 
 
 def check_sync_metrics(cfg):

@@ -99,6 +99,19 @@ class SequenceGeneratorCNN(nn.Module):
         spec = tuple((b.conv.kernel_size[0], b.stride, b.padding) + w for b, w in zip(blocks, wiring))
         return spec, [b.conv.weight for b in blocks], blocks[0].slope
 
+    def forward_tail(self, h):
+        """(B,T,256[+D]) resized audio features ++ code -> (B,T,2K): the Conv1d stage and the head, everything of the generator that
+        depends on the code (code_fit.CodeFitter iterates over this part alone)"""
+        chain = self._chain()
+        if chain is not None and ops.chain1d_usable(h, chain[0], chain[1]):
+            # U-Net + decoder blocks in one persistent launch per direction (csrc/chain1d.hip)
+            h = ops.Chain1dFn.apply(h, chain[0], chain[2], *chain[1])
+        else:
+            h = self.unet.forward_cl(h)
+            for block in list(self.decoder)[:4]:
+                h = block.forward_cl(h)
+        return conv_head(h, self.decoder[4])  # (B,T,2K): channel c = xy*K + k, i.e. already the (B,T,2,K) memory layout
+
     def forward(self, x, num_frames, code=None):
         """mel (B,80,F), code (B,D)|None -> poses (B,num_frames,2,K), generator.py:106-117."""
         num_frames = int(num_frames)
@@ -118,15 +131,7 @@ class SequenceGeneratorCNN(nn.Module):
         use_code = self.cfg.VOICE2POSE.GENERATOR.CLIP_CODE.DIMENSION is not None
         ops.stage_mark("g1d_fwd:begin")
         h = ops.ResizeConcatFn.apply(feat, code if use_code else None, num_frames)  # (B,T,256[+D])
-        chain = self._chain()
-        if chain is not None and ops.chain1d_usable(h, chain[0], chain[1]):
-            # U-Net + decoder blocks in one persistent launch per direction (csrc/chain1d.hip)
-            h = ops.Chain1dFn.apply(h, chain[0], chain[2], *chain[1])
-        else:
-            h = self.unet.forward_cl(h)
-            for block in list(self.decoder)[:4]:
-                h = block.forward_cl(h)
-        h = conv_head(h, self.decoder[4])  # (B,T,2K): channel c = xy*K + k, i.e. already the (B,T,2,K) memory layout
+        h = self.forward_tail(h)
         ops.stage_mark("g1d_fwd:end")
         if ops.STAGES is not None and h.requires_grad:
             h.register_hook(lambda g: ops.stage_mark("g1d_bwd:begin"))

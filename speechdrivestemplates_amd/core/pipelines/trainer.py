@@ -41,11 +41,13 @@ class Trainer(object):
         if not torch.cuda.is_available():
             raise RuntimeError('this engine needs an AMD GPU (no CPU fallback); torch.cuda.is_available() is False')
         torch.cuda.set_device(int(os.environ.get('LOCAL_RANK', self.get_rank() % max(1, torch.cuda.device_count()))))
-        from ...config import check_augment, check_clip_metrics, check_histograms, check_long_demo, check_motion_dist, check_sync_metrics
+        from ...config import (check_augment, check_clip_metrics, check_fit_code, check_histograms, check_long_demo, check_motion_dist,
+                               check_sync_metrics)
         check_histograms(cfg)  # SYS.HISTOGRAM_INTERVAL without SYS.TENSORBOARD: there is nowhere to write
         check_clip_metrics(cfg)  # TEST.CLIP_METRICS / TEST.PCK_ALPHAS (a Voice2Pose key)
         check_sync_metrics(cfg)  # TEST.SYNC_METRICS / SYNC_TOLERANCE / SYNC_SIGMA (a Voice2Pose key)
         check_motion_dist(cfg)  # TEST.MOTION_DIST / MOTION_DIST_EDGES (a Voice2Pose key)
+        check_fit_code(cfg)  # TEST.FIT_CODE: oracle-code validation (a Voice2Pose key)
         check_long_demo(cfg)  # DEMO.LONG_FORM and its window / smoothing / segment keys (a Voice2Pose key)
         check_augment(cfg)  # TRAIN.AUGMENT: audio augmentation inside the train step (a Voice2Pose key)
 
@@ -497,6 +499,10 @@ class Trainer(object):
         """TEST.MOTION_DIST and a pipeline that has motion histograms (Voice2Pose)"""
         return False
 
+    def uses_fit_code(self):
+        """TEST.FIT_CODE.ENABLE and a pipeline that fits template codes at validation (Voice2Pose)"""
+        return False
+
     # -- loops (trainer.py:367-427) ----------------------------------------------------------------------
     def train(self, cfg, exp_tag, resume_from=None):
         """``pipeline.train(cfg, exp_tag, args.resume_from)`` as main.py:51 calls it (trainer.py:367).  ``cfg`` is the object
@@ -559,6 +565,9 @@ class Trainer(object):
         motion_dist = self.uses_motion_dist()
         if motion_dist and self.motion_dist() is not None:
             self.motion_dist().reset()
+        fit_clip_metrics = clip_metrics and self.uses_fit_code()  # TEST.FIT_CODE: a second table takes the fitted predictions
+        if fit_clip_metrics and self.clip_metrics_fit() is not None:
+            self.clip_metrics_fit().reset()
         for t_step, batch in enumerate(test_dataloader):
             losses, res = self.test_step(batch, t_step + 1, epoch)
             for k, v in losses.items():
@@ -573,6 +582,8 @@ class Trainer(object):
             out.update(self.evaluate_epoch({k: np.concatenate(v, axis=0) for k, v in coll.items()}))
         if clip_metrics:  # every rank takes part in the all-gather of the clip tables and gets the whole set's values
             out.update(self.evaluate_clip_metrics(epoch, tag))
+        if fit_clip_metrics:  # the same all-gather for the table of the fitted predictions, its values with the suffix _fit
+            out.update(self.evaluate_clip_metrics_fit(epoch, tag))
         if sync_metrics:  # likewise: one all-gather of the synchrony tables
             out.update(self.evaluate_sync_metrics(epoch, tag))
         if motion_dist:  # likewise: one all-gather of the motion-histogram tables

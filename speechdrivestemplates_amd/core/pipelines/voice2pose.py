@@ -18,7 +18,7 @@ import torch
 from torch import nn
 
 from ... import dp, ops
-from ...config import check_augment, check_bone_loss, check_clip_metrics, check_pose_augment, check_reg_loss
+from ...config import check_augment, check_bone_loss, check_clip_metrics, check_fit_code, check_pose_augment, check_reg_loss
 from ...mel import MelSpectrogram
 from ...optim import FlatAdam
 from ..datasets.gesture_dataset import PoseTransforms
@@ -466,10 +466,13 @@ class Voice2Pose(Trainer):
         fin_p, fin_g, metrics = ops.final_metrics(results['poses_pred_batch'], results['poses_gt_batch'], stat['mean'].to(dev),
                                                   stat['std'].to(dev), stat['scale_factor'].to(dev),
                                                   bool(self.cfg.DATASET.HIERARCHICAL_POSE), True)
+        gt_normalized = results['poses_gt_batch']
         results['poses_pred_batch'], results['poses_gt_batch'] = fin_p, fin_g
         losses['L2_dist'], losses['lip_sync_error_n'] = metrics[0], metrics[1]
         if self.uses_clip_metrics():  # TEST.CLIP_METRICS: the clips' records go into the table on the device, nothing goes to the host
             self.clip_metrics(fin_p).add(fin_p, fin_g, batch['clip_index'], m)
+        if self.uses_fit_code():  # TEST.FIT_CODE: the best code the template space offers for each clip, and what the generator makes of it
+            self.fit_code_step(batch, gt_normalized, fin_g, losses, results)
         if self.uses_sync_metrics():  # TEST.SYNC_METRICS: audio onsets against the beats of both pose tensors, all on the device
             self.sync_metrics(fin_p).add(fin_p, fin_g, batch['audio'].to(dev, non_blocking=True).float(), batch['clip_index'], m)
         if self.uses_motion_dist():  # TEST.MOTION_DIST: the clips' speed / acceleration / jerk histograms go into the table on the device
@@ -492,6 +495,59 @@ class Voice2Pose(Trainer):
         keep = ('mu_pred', 'mu_gt', 'logvar_pred', 'logvar_gt', 'condition_code')
         return batch_losses, {k: v.detach().cpu().numpy() for k, v in results.items() if k in keep and v is not None}
 
+    def uses_fit_code(self):
+        return bool(self.cfg.TEST.FIT_CODE.ENABLE)
+
+    def code_fitter(self):
+        """the fitter of TEST.FIT_CODE (created by the first validation step)"""
+        if getattr(self, '_code_fitter', None) is None:
+            from ...code_fit import CodeFitter
+            self._code_fitter = CodeFitter(self.model, check_fit_code(self.cfg))
+        return self._code_fitter
+
+    def fit_code_step(self, batch, gt_normalized, fin_g, losses, results):
+        """Fit the batch's codes (code_fit.CodeFitter; it consumes no random number, so the step's other values are those of a run without
+        the key) and add the fitted prediction's values to ``losses`` / ``results``.  Everything stays on the device."""
+        dev = self.model._device()
+        fitter = self.code_fitter()
+        fit = fitter.fit(batch['audio'], gt_normalized, int(batch['num_frames'][0]))
+        stat = batch['speaker_stat']
+        fit_p, _, metrics = ops.final_metrics(fit['poses_pred'], gt_normalized, stat['mean'].to(dev), stat['std'].to(dev),
+                                              stat['scale_factor'].to(dev), bool(self.cfg.DATASET.HIERARCHICAL_POSE), True)
+        losses['L2_dist_fit'], losses['lip_sync_error_n_fit'] = metrics[0], metrics[1]
+        losses['G_reg_loss_fit'] = fit['loss_best'].mean().float()
+        losses['fit_loss_first'] = fit['loss_first'].mean().float()
+        losses['fit_code_z'] = fitter.code_z(fit['code']).float()
+        losses['fit_clips_nonfinite'] = fit['nonfinite'].float().mean()  # (the share of the batch's clips; the epoch value: of all clips)
+        if 'loss_table' in fit:
+            losses['G_reg_loss_table'] = fit['loss_table'].mean().float()
+        if self.uses_clip_metrics():
+            self.clip_metrics_fit(fit_p).add(fit_p, fin_g, batch['clip_index'], 1)
+        results['poses_pred_fit'], results['condition_code_fit'] = fit_p, fit['code']
+
+    def clip_metrics_fit(self, poses=None):
+        """the second table of clip records, for the fitted predictions (TEST.FIT_CODE with TEST.CLIP_METRICS)"""
+        if getattr(self, '_clip_metrics_fit', None) is None and poses is not None:
+            from ...clip_metrics import ClipMetricsAccumulator
+            ds = getattr(self.test_dataset, 'dataset', self.test_dataset)
+            self._clip_metrics_fit = ClipMetricsAccumulator(len(ds), poses.shape[3], check_clip_metrics(self.cfg), poses.device,
+                                                            parts=PoseTransforms.part_table())
+        return getattr(self, '_clip_metrics_fit', None)
+
+    def evaluate_clip_metrics_fit(self, epoch, tag):
+        """``evaluate_clip_metrics`` over the table of the fitted predictions; every key gets the suffix _fit"""
+        from ... import clip_metrics
+        res = self._evaluate_record_table(self.clip_metrics_fit(), clip_metrics, 'clip_fit', '', epoch, tag, lambda acc: (acc.alphas,))
+        return {k + '_fit': v for k, v in res.items()}
+
+    def demo_condition_code(self, n=1):
+        """DEMO.CODE_PATH: the (n, D) code on the device a Voice2Pose demo is conditioned on, or None (read once)"""
+        if not hasattr(self, '_demo_code'):
+            from ...code_fit import demo_code
+            v = demo_code(self.cfg)
+            self._demo_code = None if v is None else torch.from_numpy(v).to(self.model._device())
+        return None if self._demo_code is None else self._demo_code.expand(n, -1).contiguous()
+
     @torch.no_grad()
     def demo_step(self, batch, t_step=0, epoch=0, extra_id=None, interpolation_coeff=None):
         """Variable-length inference from raw audio (voice2pose.py:386-410; video + long image with SYS.RENDER_VIDEO): batch['audio'] is
@@ -503,7 +559,8 @@ class Voice2Pose(Trainer):
         if long_form:  # DEMO.LONG_FORM: windows of the training length, stitched / smoothed / reported on the GPU
             results = self.long_demo().run(batch, interpolation_coeff)
         else:
-            results = self.model(batch, self.test_dataset, return_loss=False, interpolation_coeff=interpolation_coeff)
+            results = self.model(batch, self.test_dataset, return_loss=False, interpolation_coeff=interpolation_coeff,
+                                 condition_code=self.demo_condition_code(batch['audio'].shape[0]))
             results['poses_pred_batch'] = self.test_dataset.get_final_results(results['poses_pred_batch'].detach(), batch['speaker_stat'])
         if self.is_master_process() and self.cfg.TEST.SAVE_NPZ and self.base_path is not None:
             self.save_results('DEMO', t_step, epoch, self.base_path,

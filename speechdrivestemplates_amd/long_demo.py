@@ -340,13 +340,16 @@ class LongDemo:
         self.sync = check_sync_metrics(cfg)  # TEST.SYNC_METRICS: None, or the tolerance in ticks and sigma
 
     def _code(self, dev, interpolation_coeff):
-        """one template code (1, D) for the whole recording: DEMO.CODE_INDEX (interpolated towards CODE_INDEX_B by the step's coefficient), or
+        """one template code (1, D) for the whole recording: DEMO.CODE_PATH's vector, or DEMO.CODE_INDEX (interpolated towards CODE_INDEX_B by the step's coefficient), or
         one normal draw, or one random row of the table -- drawn once, not per window"""
         import torch
         model, cfg = self.pipeline.model, self.pipeline.cfg
         code = cfg.VOICE2POSE.GENERATOR.CLIP_CODE
         if code.DIMENSION is None:
             return None
+        given = self.pipeline.demo_condition_code(1)  # DEMO.CODE_PATH: a code vector from a file (an error together with DEMO.CODE_INDEX)
+        if given is not None:
+            return given
         if code.SAMPLE_FROM_NORMAL:
             return torch.randn([1, code.DIMENSION], device=dev)
         table = model._code_table(dev)
