@@ -29,9 +29,9 @@ import numpy as np
 
 from . import _record_table
 from ._exact_model import LANES, MAX_TABLES  # noqa: F401  (public names of this module)
-from ._exact_model import MAX_COPIES, MAX_K, PARTS, _norm2, _ordered_sum, _part_sums, _quotient, check_parts, part_sizes
+from ._exact_model import MAX_COPIES, PARTS, _norm2, _ordered_sum, _part_sums, _quotient, check_parts, part_sizes
 from ._record_table import CHUNK  # noqa: F401
-from ._record_table import RecordTable, check_num_clips, chunked_records
+from ._record_table import RecordTable, check_keypoints, check_num_clips, chunked_records
 
 COLS = 40  # words of a record (SDT_CLIP_METRICS_COLS)
 FLOAT_GROUPS = ('l2_sum', 'speed_pred', 'speed_gt', 'vel_l2', 'div_sum')  # words [0, 20): group g, part p at 4 g + p
@@ -190,36 +190,24 @@ class ClipMetricsAccumulator(RecordTable):
     the step's shape (inputs that are not contiguous are made so, which allocates).  ``result`` is the only call that waits for the device.
     The state is one (num_clips + 1, 40) int64 tensor: the records, then a header row whose word 0 counts the clip indices outside the table
     (``RecordTable`` owns it, ``state``, ``table``, ``reset``, ``result`` and ``result_words``)."""
+    NOUN, NO_GPU = 'the clip metrics', _NO_GPU
 
     def __init__(self, num_clips, K, alphas, device='cuda', parts=None):
         import ctypes as C
         import torch
         from . import _lib
-        num_clips, K = check_num_clips(num_clips), int(K)
-        if not 1 <= K <= MAX_K:
-            raise ValueError('K = %d keypoints outside [1, %d]' % (K, MAX_K))
-        self.alphas, self.parts = check_alphas(list(alphas)), check_parts(parts, K)
-        self.K, self.device = K, torch.device(device)
-        if self.device.type != 'cuda':
-            raise RuntimeError(_NO_GPU)
-        if self.device.index is None:
-            self.device = torch.device('cuda', torch.cuda.current_device())
-        self._lib, self._C, self._torch = _lib.load(), C, torch
-        RecordTable.__init__(self, num_clips, self.device, COLS, 48, COLS)
+        num_clips, self.K = check_num_clips(num_clips), check_keypoints(K)
+        self.alphas, self.parts = check_alphas(list(alphas)), check_parts(parts, self.K)
+        RecordTable.__init__(self, num_clips, device, COLS, 48, COLS)
+        self._lib = _lib.load()
         self._parts_dev = torch.from_numpy(self.parts).to(self.device)
         self._alphas_c = (C.c_double * len(self.alphas))(*self.alphas)
         self._sizes_c = (C.c_int64 * 4)(*part_sizes(self.parts))
         self._work_shape, self._work = None, None
 
-    def _stream(self):
-        return self._torch.cuda.current_stream(self.device).cuda_stream
-
-    def _p(self, t):
-        return None if t is None else self._C.c_void_p(t.data_ptr())
-
     def _workspace(self, R, T, m):
         if self._work_shape != (R, T, m):
-            torch = self._torch
+            import torch
             self._work = (torch.empty(R * T * 32, dtype=torch.int64, device=self.device),
                           torch.empty((R, COLS), dtype=torch.int64, device=self.device),
                           torch.empty(R // m * T * 4, dtype=torch.float64, device=self.device) if m > 1 else None)
@@ -228,40 +216,24 @@ class ClipMetricsAccumulator(RecordTable):
 
     def row_records(self, pred, gt):
         """the (R, 40) records of the rows alone (sdt_clip_metrics_rows_f64), a tensor that the next call overwrites"""
+        import torch
         from . import _lib
         pred, gt = self._poses(pred), self._poses(gt)
         if pred.shape != gt.shape:
             raise ValueError('prediction %s and ground truth %s differ in shape' % (tuple(pred.shape), tuple(gt.shape)))
         R, T = pred.shape[:2]
         work, rows, _ = self._workspace(R, T, 1)
-        with self._torch.cuda.device(self.device):
+        with torch.cuda.device(self.device):
             _lib.check(self._lib.sdt_clip_metrics_rows_f64(self._p(pred), self._p(gt), self._p(self._parts_dev), self._alphas_c, len(self.alphas),
                                                            R, T, self.K, self._p(work), self._p(rows), self._stream()))
         return rows
 
-    def _poses(self, x):
-        torch = self._torch
-        if not torch.is_tensor(x) or x.device != self.device:
-            raise RuntimeError('the clip metrics take tensors on %s; %s' % (self.device, _NO_GPU))
-        if x.dtype != torch.float64 or x.ndim != 4 or x.shape[2] != 2 or x.shape[3] != self.K or x.shape[0] < 1 or x.shape[1] < 1:
-            raise TypeError('poses must be (rows, frames, 2, %d) float64, got %s %s' % (self.K, tuple(x.shape), x.dtype))
-        return x.detach().contiguous()
-
     def add(self, pred, gt, clip_index, multiple=1):
         """one validation step: rows (multiple * B, T, 2, K) of final poses, copy j of clip b in row j * B + b; ``clip_index``: the B table rows
         (an int64 tensor of B entries, or of multiple * B as ``mutiply_batch`` leaves it: the first B are read)"""
+        import torch
         from . import _lib
-        torch, m = self._torch, int(multiple)
-        if not 1 <= m <= MAX_COPIES:
-            raise ValueError('%d copies outside [1, %d]' % (m, MAX_COPIES))
-        pred, gt = self._poses(pred), self._poses(gt)
-        R, T = pred.shape[:2]
-        if pred.shape != gt.shape or R % m:
-            raise ValueError('prediction %s and ground truth %s must be %d copies of one batch' % (tuple(pred.shape), tuple(gt.shape), m))
-        B = R // m
-        if not torch.is_tensor(clip_index) or clip_index.dtype != torch.int64 or clip_index.ndim != 1 or clip_index.numel() not in (B, R):
-            raise TypeError('clip_index must be an int64 tensor of %d (or %d) entries' % (B, R))
-        idx = clip_index[:B].to(self.device, non_blocking=True).contiguous()
+        pred, gt, idx, B, R, T, m = self._step(pred, gt, clip_index, multiple)
         work, rows, div = self._workspace(R, T, m)
         with torch.cuda.device(self.device):
             s = self._stream()

@@ -325,13 +325,18 @@ def check_clip_metrics(cfg):
         raise ValueError("TEST.PCK_ALPHAS: every alpha must be a finite number > 0, got %r" % (alphas,))
     if not on:
         return None
+    _check_clip_table_key(cfg, "TEST.CLIP_METRICS", "PCK, part errors, speed and diversity of predicted gestures",
+                          " (the pairwise diversity of the copies)")
+    return tuple(float(a) for a in alphas)
+
+
+def _check_clip_table_key(cfg, key, what, why_multiple=""):
+    """what every per-clip validation table asks of the run: the Voice2Pose pipeline, and TEST.MULTIPLE from 1 to 16"""
     if cfg.PIPELINE_TYPE != "Voice2Pose":
-        raise ValueError("TEST.CLIP_METRICS is a Voice2Pose key (PCK, part errors, speed and diversity of predicted gestures), got "
-                         "PIPELINE_TYPE %r" % (cfg.PIPELINE_TYPE,))
+        raise ValueError("%s is a Voice2Pose key (%s), got PIPELINE_TYPE %r" % (key, what, cfg.PIPELINE_TYPE))
     m = cfg.TEST.MULTIPLE
     if isinstance(m, bool) or not isinstance(m, int) or not 1 <= m <= 16:
-        raise ValueError("TEST.CLIP_METRICS takes TEST.MULTIPLE from 1 to 16 (the pairwise diversity of the copies), got %r" % (m,))
-    return tuple(float(a) for a in alphas)
+        raise ValueError("%s takes TEST.MULTIPLE from 1 to 16%s, got %r" % (key, why_multiple, m))
 
 
 def _is_int(v):
@@ -394,17 +399,12 @@ def check_sync_metrics(cfg):
         raise ValueError("TEST.SYNC_SIGMA must be a finite number of seconds > 0, got %r" % (sigma,))
     if not on:
         return None
-    if cfg.PIPELINE_TYPE != "Voice2Pose":
-        raise ValueError("TEST.SYNC_METRICS is a Voice2Pose key (audio onsets against the beats of predicted gestures), got PIPELINE_TYPE %r"
-                         % (cfg.PIPELINE_TYPE,))
+    _check_clip_table_key(cfg, "TEST.SYNC_METRICS", "audio onsets against the beats of predicted gestures")
     if cfg.DATASET.AUDIO_SR != 16000:
         raise ValueError("TEST.SYNC_METRICS needs DATASET.AUDIO_SR 16000 (an audio hop of 160 samples is 3 ticks of 1/300 s), got %r"
                          % (cfg.DATASET.AUDIO_SR,))
     if cfg.DATASET.FPS != 15:
         raise ValueError("TEST.SYNC_METRICS needs DATASET.FPS 15 (a pose frame is 20 ticks of 1/300 s), got %r" % (cfg.DATASET.FPS,))
-    m = cfg.TEST.MULTIPLE
-    if isinstance(m, bool) or not isinstance(m, int) or not 1 <= m <= 16:
-        raise ValueError("TEST.SYNC_METRICS takes TEST.MULTIPLE from 1 to 16, got %r" % (m,))
     return {'tol_ticks': ticks, 'sigma': float(sigma)}
 
 
@@ -425,12 +425,7 @@ def check_motion_dist(cfg):
         edges = tuple(tuple(float(e) for e in row) for row in edges)
     if not on:
         return None
-    if cfg.PIPELINE_TYPE != "Voice2Pose":
-        raise ValueError("TEST.MOTION_DIST is a Voice2Pose key (motion histograms of predicted gestures against the ground truth), got "
-                         "PIPELINE_TYPE %r" % (cfg.PIPELINE_TYPE,))
-    m = cfg.TEST.MULTIPLE
-    if isinstance(m, bool) or not isinstance(m, int) or not 1 <= m <= 16:
-        raise ValueError("TEST.MOTION_DIST takes TEST.MULTIPLE from 1 to 16, got %r" % (m,))
+    _check_clip_table_key(cfg, "TEST.MOTION_DIST", "motion histograms of predicted gestures against the ground truth")
     return {'edges': edges}
 
 

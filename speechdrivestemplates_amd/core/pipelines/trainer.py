@@ -483,25 +483,9 @@ class Trainer(object):
     def evaluate_epoch(self, results_dict):
         return {}
 
-    def uses_device_fgd(self):
-        """SYS.DEVICE_FGD and a pipeline that has an epoch-level FGD (Voice2Pose with a pose encoder)"""
-        return False
-
-    def uses_clip_metrics(self):
-        """TEST.CLIP_METRICS and a pipeline that has per-clip metrics (Voice2Pose)"""
-        return False
-
-    def uses_sync_metrics(self):
-        """TEST.SYNC_METRICS and a pipeline that has speech-gesture synchrony metrics (Voice2Pose)"""
-        return False
-
-    def uses_motion_dist(self):
-        """TEST.MOTION_DIST and a pipeline that has motion histograms (Voice2Pose)"""
-        return False
-
-    def uses_fit_code(self):
-        """TEST.FIT_CODE.ENABLE and a pipeline that fits template codes at validation (Voice2Pose)"""
-        return False
+    def val_observers(self):
+        """the ordered list of what this pipeline accumulates on the device at validation (val_observers.py); the base pipeline: nothing"""
+        return []
 
     # -- loops (trainer.py:367-427) ----------------------------------------------------------------------
     def train(self, cfg, exp_tag, resume_from=None):
@@ -553,21 +537,9 @@ class Trainer(object):
         self.model.eval()
         tic = time.time()
         sums, coll = {}, {}
-        device_fgd = self.uses_device_fgd()
-        if device_fgd and self.device_fgd() is not None:
-            self.device_fgd().reset()
-        clip_metrics = self.uses_clip_metrics()
-        if clip_metrics and self.clip_metrics() is not None:
-            self.clip_metrics().reset()
-        sync_metrics = self.uses_sync_metrics()
-        if sync_metrics and self.sync_metrics() is not None:
-            self.sync_metrics().reset()
-        motion_dist = self.uses_motion_dist()
-        if motion_dist and self.motion_dist() is not None:
-            self.motion_dist().reset()
-        fit_clip_metrics = clip_metrics and self.uses_fit_code()  # TEST.FIT_CODE: a second table takes the fitted predictions
-        if fit_clip_metrics and self.clip_metrics_fit() is not None:
-            self.clip_metrics_fit().reset()
+        observers = [o for o in self.val_observers() if o.enabled(self.cfg)]
+        for o in observers:
+            o.reset()
         for t_step, batch in enumerate(test_dataloader):
             losses, res = self.test_step(batch, t_step + 1, epoch)
             for k, v in losses.items():
@@ -576,18 +548,10 @@ class Trainer(object):
                 coll.setdefault(k, []).append(v)
         self.check_kernels_all_ranks()
         out = {k: v / self.num_test_samples for k, v in sums.items()}
-        if device_fgd:  # every rank takes part in the all-gather of the moment states and gets the whole set's value
-            out.update(self.evaluate_epoch_device())
-        elif coll and self.is_master_process():
+        if coll and self.is_master_process():  # (nothing was collected when the features stayed on the device)
             out.update(self.evaluate_epoch({k: np.concatenate(v, axis=0) for k, v in coll.items()}))
-        if clip_metrics:  # every rank takes part in the all-gather of the clip tables and gets the whole set's values
-            out.update(self.evaluate_clip_metrics(epoch, tag))
-        if fit_clip_metrics:  # the same all-gather for the table of the fitted predictions, its values with the suffix _fit
-            out.update(self.evaluate_clip_metrics_fit(epoch, tag))
-        if sync_metrics:  # likewise: one all-gather of the synchrony tables
-            out.update(self.evaluate_sync_metrics(epoch, tag))
-        if motion_dist:  # likewise: one all-gather of the motion-histogram tables
-            out.update(self.evaluate_motion_dist(epoch, tag))
+        for o in observers:  # collective: every rank takes part in the all-gather of the states and gets the whole set's values
+            out.update(o.epoch(epoch, tag))
         if self.is_master_process():
             logging.info('[VAL] epoch: %d  val_time: %.1f min  ' % (epoch, (time.time() - tic) / 60) +
                          ''.join('%s: %.5f  ' % (k, float(v)) for k, v in out.items()))

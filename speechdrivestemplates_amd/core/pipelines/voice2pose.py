@@ -10,19 +10,19 @@ Deliberate, documented differences from the reference:
     SYS.DDP_UNSYNCED_D reproduces that);
   * per-loss scalars are reduced to rank 0 in one packed collective, only on logging steps.
 """
-import logging
-import os
 from collections import OrderedDict
+from types import SimpleNamespace
 
 import torch
 from torch import nn
 
 from ... import dp, ops
-from ...config import check_augment, check_bone_loss, check_clip_metrics, check_fit_code, check_pose_augment, check_reg_loss
+from ...config import check_augment, check_bone_loss, check_fit_code, check_pose_augment, check_reg_loss
 from ...mel import MelSpectrogram
 from ...optim import FlatAdam
 from ..datasets.gesture_dataset import PoseTransforms
 from ..networks import get_model
+from . import val_observers as vo
 from .trainer import Trainer
 
 
@@ -295,6 +295,9 @@ class Voice2PoseModel(nn.Module):
 class Voice2Pose(Trainer):
     def __init__(self, cfg) -> None:
         super().__init__(cfg)
+        self.fgd_observer, self.clip_observer, self.sync_observer, self.motion_observer = (
+            vo.DeviceFGD(self), vo.ClipMetrics(self), vo.SyncMetrics(self), vo.MotionDist(self))
+        self._val_observers = [self.fgd_observer, self.clip_observer, vo.FitClipMetrics(self), self.sync_observer, self.motion_observer]
 
     def setup_model(self, cfg, state_dict=None, external_codes=None):
         # kernel routing this pipeline's configuration asks for -- set UNCONDITIONALLY (defaults included: a pipeline built after a bf16 one in the
@@ -469,14 +472,12 @@ class Voice2Pose(Trainer):
         gt_normalized = results['poses_gt_batch']
         results['poses_pred_batch'], results['poses_gt_batch'] = fin_p, fin_g
         losses['L2_dist'], losses['lip_sync_error_n'] = metrics[0], metrics[1]
-        if self.uses_clip_metrics():  # TEST.CLIP_METRICS: the clips' records go into the table on the device, nothing goes to the host
-            self.clip_metrics(fin_p).add(fin_p, fin_g, batch['clip_index'], m)
-        if self.uses_fit_code():  # TEST.FIT_CODE: the best code the template space offers for each clip, and what the generator makes of it
-            self.fit_code_step(batch, gt_normalized, fin_g, losses, results)
-        if self.uses_sync_metrics():  # TEST.SYNC_METRICS: audio onsets against the beats of both pose tensors, all on the device
-            self.sync_metrics(fin_p).add(fin_p, fin_g, batch['audio'].to(dev, non_blocking=True).float(), batch['clip_index'], m)
-        if self.uses_motion_dist():  # TEST.MOTION_DIST: the clips' speed / acceleration / jerk histograms go into the table on the device
-            self.motion_dist(fin_p).add(fin_p, fin_g, batch['clip_index'], m)
+        ctx = SimpleNamespace(batch=batch, fin_p=fin_p, fin_g=fin_g, results=results, losses=losses, multiple=m, device=dev)
+        if self.cfg.TEST.FIT_CODE.ENABLE:  # the best code the template space offers for each clip, and what the generator makes of it
+            self.fit_code_step(ctx, gt_normalized)
+        observers = [o for o in self.val_observers() if o.enabled(self.cfg)]
+        for o in observers:  # everything stays on the device
+            o.step(ctx)
         if self.cfg.SYS.DISTRIBUTED:
             dp.reduce_scalars(losses)
         if self.is_master_process():
@@ -488,15 +489,10 @@ class Voice2Pose(Trainer):
             if t_step % self.result_saving_interval_test == 0 and self.cfg.TEST.SAVE_VIDEO and self.rendering() and self.base_path is not None:
                 self.write_pair_video(tag, fin_p[0], fin_g[0], t_step, epoch, audio=batch['audio'])  # voice2pose.py:372-378
         batch_losses = {k: v.detach() * self.cfg.TEST.BATCH_SIZE for k, v in losses.items()}
-        if self.uses_device_fgd():  # SYS.DEVICE_FGD: the features go into the moment states on the device, nothing goes to the host
-            ops.join_side_stream()
-            self.device_fgd(results['mu_pred']).add(results['mu_pred'], results['mu_gt'], results['logvar_pred'], results['logvar_gt'])
+        if self.fgd_observer in observers:  # SYS.DEVICE_FGD: the features stay on the device
             return batch_losses, {}
         keep = ('mu_pred', 'mu_gt', 'logvar_pred', 'logvar_gt', 'condition_code')
         return batch_losses, {k: v.detach().cpu().numpy() for k, v in results.items() if k in keep and v is not None}
-
-    def uses_fit_code(self):
-        return bool(self.cfg.TEST.FIT_CODE.ENABLE)
 
     def code_fitter(self):
         """the fitter of TEST.FIT_CODE (created by the first validation step)"""
@@ -505,15 +501,16 @@ class Voice2Pose(Trainer):
             self._code_fitter = CodeFitter(self.model, check_fit_code(self.cfg))
         return self._code_fitter
 
-    def fit_code_step(self, batch, gt_normalized, fin_g, losses, results):
+    def fit_code_step(self, ctx, gt_normalized):
         """Fit the batch's codes (code_fit.CodeFitter; it consumes no random number, so the step's other values are those of a run without
-        the key) and add the fitted prediction's values to ``losses`` / ``results``.  Everything stays on the device."""
-        dev = self.model._device()
+        the key), add the fitted prediction's values to the step's losses / results and leave its final poses in ``ctx.fit_p``.  Everything
+        stays on the device."""
+        batch, losses, results, dev = ctx.batch, ctx.losses, ctx.results, ctx.device
         fitter = self.code_fitter()
         fit = fitter.fit(batch['audio'], gt_normalized, int(batch['num_frames'][0]))
         stat = batch['speaker_stat']
-        fit_p, _, metrics = ops.final_metrics(fit['poses_pred'], gt_normalized, stat['mean'].to(dev), stat['std'].to(dev),
-                                              stat['scale_factor'].to(dev), bool(self.cfg.DATASET.HIERARCHICAL_POSE), True)
+        ctx.fit_p, _, metrics = ops.final_metrics(fit['poses_pred'], gt_normalized, stat['mean'].to(dev), stat['std'].to(dev),
+                                                  stat['scale_factor'].to(dev), bool(self.cfg.DATASET.HIERARCHICAL_POSE), True)
         losses['L2_dist_fit'], losses['lip_sync_error_n_fit'] = metrics[0], metrics[1]
         losses['G_reg_loss_fit'] = fit['loss_best'].mean().float()
         losses['fit_loss_first'] = fit['loss_first'].mean().float()
@@ -521,24 +518,7 @@ class Voice2Pose(Trainer):
         losses['fit_clips_nonfinite'] = fit['nonfinite'].float().mean()  # (the share of the batch's clips; the epoch value: of all clips)
         if 'loss_table' in fit:
             losses['G_reg_loss_table'] = fit['loss_table'].mean().float()
-        if self.uses_clip_metrics():
-            self.clip_metrics_fit(fit_p).add(fit_p, fin_g, batch['clip_index'], 1)
-        results['poses_pred_fit'], results['condition_code_fit'] = fit_p, fit['code']
-
-    def clip_metrics_fit(self, poses=None):
-        """the second table of clip records, for the fitted predictions (TEST.FIT_CODE with TEST.CLIP_METRICS)"""
-        if getattr(self, '_clip_metrics_fit', None) is None and poses is not None:
-            from ...clip_metrics import ClipMetricsAccumulator
-            ds = getattr(self.test_dataset, 'dataset', self.test_dataset)
-            self._clip_metrics_fit = ClipMetricsAccumulator(len(ds), poses.shape[3], check_clip_metrics(self.cfg), poses.device,
-                                                            parts=PoseTransforms.part_table())
-        return getattr(self, '_clip_metrics_fit', None)
-
-    def evaluate_clip_metrics_fit(self, epoch, tag):
-        """``evaluate_clip_metrics`` over the table of the fitted predictions; every key gets the suffix _fit"""
-        from ... import clip_metrics
-        res = self._evaluate_record_table(self.clip_metrics_fit(), clip_metrics, 'clip_fit', '', epoch, tag, lambda acc: (acc.alphas,))
-        return {k + '_fit': v for k, v in res.items()}
+        results['poses_pred_fit'], results['condition_code_fit'] = ctx.fit_p, fit['code']
 
     def demo_condition_code(self, n=1):
         """DEMO.CODE_PATH: the (n, D) code on the device a Voice2Pose demo is conditioned on, or None (read once)"""
@@ -605,131 +585,22 @@ class Voice2Pose(Trainer):
         den = lg.max(-1, keepdim=True).values + 1e-4
         return {'L2_dist': l2.mean(), 'lip_sync_error_n': torch.abs(lp / den - lg / den).mean()}
 
-    def uses_device_fgd(self):
-        return bool(getattr(self.cfg.SYS, 'DEVICE_FGD', False)) and self.cfg.VOICE2POSE.POSE_ENCODER.NAME is not None
+    def val_observers(self):
+        """device FGD, clip metrics, fitted-clip metrics, synchrony, motion histograms: this order is the key order of validate()'s result.
+        The four lookups below give an observer's accumulator (None before the first validation step with its key on)."""
+        return self._val_observers
 
-    def device_fgd(self, mu=None):
-        """the accumulator of mu ++ logvar rows (created at the first step, which knows the code width and the device)"""
-        if getattr(self, '_device_fgd', None) is None and mu is not None:
-            from ...fgd import FGDAccumulator
-            self._device_fgd = FGDAccumulator(2 * mu.shape[1], mu.device)
-        return getattr(self, '_device_fgd', None)
+    def device_fgd(self):
+        return self.fgd_observer.acc
 
-    def evaluate_epoch_device(self):
-        """FGD_mu (the leading block of the mu ++ logvar moments) and FGD_mu_logvar over the rows every rank delivered: the ranks' states are
-        all-gathered and merged in rank order, so every rank reports the same value.  A non-finite feature is a warning and a NaN metric,
-        not the end of a training run."""
-        from ...fgd import describe_error
-        acc = self.device_fgd()
-        if acc is None:  # no validation step ran
-            return {}
-        gathered = None
-        if self.cfg.SYS.DISTRIBUTED:
-            gathered = [torch.empty_like(acc.states()) for _ in range(torch.distributed.get_world_size())]
-            torch.distributed.all_gather(gathered, acc.states())  # (the list form: nccl and gloo both have it)
-        out = {}
-        for key, dim_used in (('FGD_mu', acc.dim // 2), ('FGD_mu_logvar', acc.dim)):
-            res = acc.result(dim_used=dim_used, gathered=gathered, strict=False)
-            if res['err']:
-                logging.warning('[VAL] %s: %s' % (key, describe_error(res)))
-            out[key] = res['fgd']
-        return out
+    def clip_metrics(self):
+        return self.clip_observer.acc
 
-    def uses_clip_metrics(self):
-        return bool(getattr(self.cfg.TEST, 'CLIP_METRICS', False))
+    def sync_metrics(self):
+        return self.sync_observer.acc
 
-    def clip_metrics(self, poses=None):
-        """the table of clip records (created at the first step, which knows the keypoint count and the device); one row per clip of the
-        validation set, addressed by the batch's 'clip_index'"""
-        if getattr(self, '_clip_metrics', None) is None and poses is not None:
-            from ...clip_metrics import ClipMetricsAccumulator
-            ds = getattr(self.test_dataset, 'dataset', self.test_dataset)  # (a Subset keeps the indices of the set it was cut from)
-            self._clip_metrics = ClipMetricsAccumulator(len(ds), poses.shape[3], check_clip_metrics(self.cfg), poses.device,
-                                                        parts=PoseTransforms.part_table())
-        return getattr(self, '_clip_metrics', None)
-
-    def evaluate_clip_metrics(self, epoch, tag):
-        """PCK, part errors, speed ratio, velocity error and diversity over the clips every rank delivered: the ranks' tables are all-gathered
-        and clip by clip the lowest rank that has a record gives it, so every rank reports the same bits.  A clip with a non-finite sum is
-        left out, counted and warned about; so is a clip index outside the table."""
-        from ... import clip_metrics
-        return self._evaluate_record_table(self.clip_metrics(), clip_metrics, 'clip', '', epoch, tag, lambda acc: (acc.alphas,))
-
-    def _evaluate_record_table(self, acc, module, label, prefix, epoch, tag, save_args):
-        """the epoch values of one record table (``module``: clip_metrics, sync_metrics or motion_dist): all-gather the ranks' states, ``result``, warn
-        about clips left out, save the merged table with TEST.SAVE_NPZ (``save_args(acc)``: what ``module.save_table`` takes after the
-        records) and drop the bookkeeping entries"""
-        if acc is None:  # no validation step ran
-            return {}
-        gathered = None
-        if self.cfg.SYS.DISTRIBUTED:
-            gathered = [torch.empty_like(acc.state()) for _ in range(torch.distributed.get_world_size())]
-            torch.distributed.all_gather(gathered, acc.state())  # (the list form: nccl and gloo both have it)
-        res = acc.result(gathered)
-        if res[prefix + 'clips_nonfinite'] or res[prefix + 'index_errors']:
-            logging.warning('[VAL] %s metrics: %d clip(s) left out for a non-finite sum, %d clip index(es) outside the table of %d'
-                            % (label, res[prefix + 'clips_nonfinite'], res[prefix + 'index_errors'], acc.num_clips))
-        if self.is_master_process() and self.cfg.TEST.SAVE_NPZ and self.base_path is not None:
-            d = os.path.join(self.base_path, 'results')
-            os.makedirs(d, exist_ok=True)
-            tables = [acc.table()] if gathered is None else [g[:acc.num_clips] for g in gathered]
-            module.save_table('%s/epoch%d-%s-%s_metrics.npz' % (d, epoch, tag, label), module.merge_tables([t.cpu().numpy() for t in tables]),
-                              *save_args(acc))
-        return {k: v for k, v in res.items() if k not in module.BOOKKEEPING}
-
-    def uses_sync_metrics(self):
-        return bool(getattr(self.cfg.TEST, 'SYNC_METRICS', False))
-
-    def sync_metrics(self, poses=None):
-        """the table of synchrony records (created at the first step, which knows the keypoint count and the device); one row per clip of
-        the validation set, addressed by the batch's 'clip_index'"""
-        if getattr(self, '_sync_metrics', None) is None and poses is not None:
-            from ...config import check_sync_metrics
-            from ...sync_metrics import SyncAccumulator
-            opts = check_sync_metrics(self.cfg)
-            ds = getattr(self.test_dataset, 'dataset', self.test_dataset)  # (a Subset keeps the indices of the set it was cut from)
-            self._sync_metrics = SyncAccumulator(len(ds), poses.shape[3], opts['tol_ticks'], opts['sigma'], poses.device,
-                                                 parts=PoseTransforms.part_table())
-        return getattr(self, '_sync_metrics', None)
-
-    def evaluate_sync_metrics(self, epoch, tag):
-        """precision, recall, offset and alignment of the beats against the audio onsets over the clips every rank delivered, merged as
-        ``evaluate_clip_metrics`` merges its tables.  A clip with a non-finite sum is left out, counted and warned about."""
-        from ... import sync_metrics
-        return self._evaluate_record_table(self.sync_metrics(), sync_metrics, 'sync', 'sync_', epoch, tag, lambda acc: (acc.tol, acc.sigma))
-
-    def uses_motion_dist(self):
-        return bool(getattr(self.cfg.TEST, 'MOTION_DIST', False))
-
-    def motion_dist(self, poses=None):
-        """the table of motion-histogram records (created at the first step, which knows the keypoint count and the device); one row per clip
-        of the validation set, addressed by the batch's 'clip_index'"""
-        if getattr(self, '_motion_dist', None) is None and poses is not None:
-            from ...config import check_motion_dist
-            from ...motion_dist import MotionDistAccumulator
-            ds = getattr(self.test_dataset, 'dataset', self.test_dataset)  # (a Subset keeps the indices of the set it was cut from)
-            self._motion_dist = MotionDistAccumulator(len(ds), poses.shape[3], check_motion_dist(self.cfg)['edges'], poses.device,
-                                                      parts=PoseTransforms.part_table())
-        return getattr(self, '_motion_dist', None)
-
-    def evaluate_motion_dist(self, epoch, tag):
-        """Hellinger distances of the speed, acceleration and jerk histograms (prediction against ground truth, and the noise floor between
-        two halves of the ground truth) and the magnitude ratios over the clips every rank delivered, merged as ``evaluate_clip_metrics``
-        merges its tables.  A clip with a NaN term or a non-finite sum is left out, counted and warned about.  With SYS.TENSORBOARD the
-        master also writes the merged histograms."""
-        from ... import motion_dist
-        acc = self.motion_dist()
-        out = self._evaluate_record_table(acc, motion_dist, 'motion', 'motion_', epoch, tag, lambda a: (a.edges, a.histograms()))
-        tb = getattr(self, 'tb_writer', None)
-        if acc is not None and tb is not None and self.is_master_process():
-            hist = acc.histograms()  # (the merged histograms of the result() above)
-            for s, source in enumerate(motion_dist.SOURCES):
-                for o, order in enumerate(motion_dist.ORDERS):
-                    for p, part in enumerate(motion_dist.PARTS):
-                        tb.add_histogram_raw('%s/motion/%s_%s_%s' % (tag.lower(), order, source, part),
-                                             *motion_dist.tb_histogram_fields(hist[s, o, p], acc.edges[o]), step=epoch)
-            tb.flush()
-        return out
+    def motion_dist(self):
+        return self.motion_observer.acc
 
     def evaluate_epoch(self, results_dict):
         from ...fgd import compute_fgd

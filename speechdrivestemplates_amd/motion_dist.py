@@ -40,7 +40,7 @@ import numpy as np
 
 from . import _record_table
 from ._exact_model import MAX_COPIES, MAX_K, PARTS, _norm2, _ordered_sum, _part_sums, check_parts
-from ._record_table import RecordTable, check_num_clips, chunked_records
+from ._record_table import RecordTable, check_keypoints, check_num_clips
 from .clip_metrics import load_poses
 
 NB, NE = 32, 31  # bins and inner edges per order
@@ -320,57 +320,39 @@ class MotionDistAccumulator(RecordTable):
     is one (num_clips + 1, 316) int64 tensor (``RecordTable`` owns it, ``state``, ``table``, ``reset``, ``result`` and ``result_words``);
     ``histograms`` gives the merged histograms of the last ``result``."""
 
+    NOUN, NO_GPU = 'the motion histograms', _NO_GPU
+
     def __init__(self, num_clips, K, edges=None, device='cuda', parts=None):
-        import ctypes as C
         import torch
         from . import _lib
-        num_clips, K = check_num_clips(num_clips), int(K)
-        if not 1 <= K <= MAX_K:
-            raise ValueError('K = %d keypoints outside [1, %d]' % (K, MAX_K))
-        self.edges, self.parts = check_edges(edges), check_parts(parts, K)
-        self.K, self.device = K, torch.device(device)
-        if self.device.type != 'cuda':
-            raise RuntimeError(_NO_GPU)
-        if self.device.index is None:
-            self.device = torch.device('cuda', torch.cuda.current_device())
-        self._lib, self._C, self._torch = _lib.load(), C, torch
-        RecordTable.__init__(self, num_clips, self.device, COLS, CHUNK_WORDS, OUT_COLS)
-        if self._lib.sdt_motion_dist_epoch_work_words(num_clips) != self._epoch_work.numel():
+        num_clips, self.K = check_num_clips(num_clips), check_keypoints(K)
+        self.edges, self.parts = check_edges(edges), check_parts(parts, self.K)
+        RecordTable.__init__(self, num_clips, device, COLS, CHUNK_WORDS, OUT_COLS)
+        self._lib = _lib.load()
+        if self._lib.sdt_motion_dist_epoch_work_words(self.num_clips) != self._epoch_work.numel():
             raise RuntimeError('the library asks for %d workspace words, this binding allocates %d'
-                               % (self._lib.sdt_motion_dist_epoch_work_words(num_clips), self._epoch_work.numel()))
+                               % (self._lib.sdt_motion_dist_epoch_work_words(self.num_clips), self._epoch_work.numel()))
         self._parts_dev = torch.from_numpy(self.parts).to(self.device)
         self._edges_dev = torch.from_numpy(edge_table(self.edges)).to(self.device)
         self._hist = torch.zeros((2, 3, 4, NB), dtype=torch.int64, device=self.device)
         self._rows = None
 
-    def _stream(self):
-        return self._torch.cuda.current_stream(self.device).cuda_stream
-
-    def _p(self, t):
-        return None if t is None else self._C.c_void_p(t.data_ptr())
-
-    def _poses(self, x):
-        torch = self._torch
-        if not torch.is_tensor(x) or x.device != self.device:
-            raise RuntimeError('the motion histograms take tensors on %s; %s' % (self.device, _NO_GPU))
-        if x.dtype != torch.float64 or x.ndim != 4 or x.shape[2] != 2 or x.shape[3] != self.K or x.shape[0] < 1 or x.shape[1] < 1:
-            raise TypeError('poses must be (rows, frames, 2, %d) float64, got %s %s' % (self.K, tuple(x.shape), x.dtype))
-        return x.detach().contiguous()
-
     def _row_workspace(self, R):
         if self._rows is None or self._rows.shape[0] != R:
-            self._rows = self._torch.empty((R, COLS), dtype=self._torch.int64, device=self.device)
+            import torch
+            self._rows = torch.empty((R, COLS), dtype=torch.int64, device=self.device)
         return self._rows
 
     def row_records(self, pred, gt):
         """the (R, 316) records of the rows alone (sdt_motion_dist_rows_f64), a tensor that the next call overwrites"""
+        import torch
         from . import _lib
         pred, gt = self._poses(pred), self._poses(gt)
         if pred.shape != gt.shape:
             raise ValueError('prediction %s and ground truth %s differ in shape' % (tuple(pred.shape), tuple(gt.shape)))
         R, T = pred.shape[:2]
         rows = self._row_workspace(R)
-        with self._torch.cuda.device(self.device):
+        with torch.cuda.device(self.device):
             _lib.check(self._lib.sdt_motion_dist_rows_f64(self._p(pred), self._p(gt), self._p(self._parts_dev), self._p(self._edges_dev),
                                                           R, T, self.K, self._p(rows), self._stream()))
         return rows
@@ -378,18 +360,9 @@ class MotionDistAccumulator(RecordTable):
     def add(self, pred, gt, clip_index, multiple=1):
         """one validation step: rows (multiple * B, T, 2, K) of final poses, copy j of clip b in row j * B + b; ``clip_index``: the B table rows
         (an int64 tensor of B entries, or of multiple * B as ``mutiply_batch`` leaves it: the first B are read)"""
+        import torch
         from . import _lib
-        torch, m = self._torch, int(multiple)
-        if not 1 <= m <= MAX_COPIES:
-            raise ValueError('%d copies outside [1, %d]' % (m, MAX_COPIES))
-        pred, gt = self._poses(pred), self._poses(gt)
-        R, T = pred.shape[:2]
-        if pred.shape != gt.shape or R % m:
-            raise ValueError('prediction %s and ground truth %s must be %d copies of one batch' % (tuple(pred.shape), tuple(gt.shape), m))
-        B = R // m
-        if not torch.is_tensor(clip_index) or clip_index.dtype != torch.int64 or clip_index.ndim != 1 or clip_index.numel() not in (B, R):
-            raise TypeError('clip_index must be an int64 tensor of %d (or %d) entries' % (B, R))
-        idx = clip_index[:B].to(self.device, non_blocking=True).contiguous()
+        pred, gt, idx, B, R, T, m = self._step(pred, gt, clip_index, multiple)
         rows = self._row_workspace(R)
         with torch.cuda.device(self.device):
             s = self._stream()

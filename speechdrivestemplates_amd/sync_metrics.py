@@ -27,9 +27,9 @@ import numpy as np
 
 from . import _record_table
 from ._exact_model import MAX_TABLES  # noqa: F401  (public names of this module)
-from ._exact_model import MAX_COPIES, MAX_K, PARTS, _butterfly_wave, _norm2, _ordered_sum, _part_sums, _quotient, check_parts
+from ._exact_model import MAX_COPIES, PARTS, _butterfly_wave, _norm2, _ordered_sum, _part_sums, _quotient, check_parts
 from ._record_table import CHUNK  # noqa: F401
-from ._record_table import RecordTable, check_num_clips, chunked_records
+from ._record_table import RecordTable, check_keypoints, check_num_clips, check_poses, chunked_records, cuda_device, ptr, stream
 
 SAMPLE_RATE, FPS, TICKS = 16000, 15, 300
 HOP, FRAME, HOP_TICKS, FRAME_TICKS = 160, 320, 3, 20
@@ -49,6 +49,7 @@ VALUE_PAIRS = ('sync_precision', 'sync_precision_gt', 'sync_recall', 'sync_recal
 OUT_ONSETS_PER_S, OUT_SEEN, OUT_NONFINITE, OUT_INDEX_ERRORS = 18, 20, 21, 22
 BOOKKEEPING = ('sync_clips_seen', 'sync_index_errors')  # entries of result() that are not metrics
 MAX_HOPS, MAX_FRAMES = 1 << 28, 1 << 24
+_NOUN = 'the synchrony metrics'
 _NO_GPU = 'the synchrony metrics are computed on the GPU (csrc/sync_metrics.hip); there is no CPU fallback (sync_model is the numpy contract)'
 assert len(COLUMN_NAMES) == COLS
 
@@ -320,34 +321,26 @@ class _Device:
     """the two launches of the detector and of a pose tensor's rows, with a workspace that is kept while the shape stays"""
 
     def __init__(self, K, tol, table, device, parts=None, delta=DELTA, floor=FLOOR, gamma=GAMMA):
-        import ctypes as C
         import torch
         from . import _lib
-        K = int(K)
-        if not 1 <= K <= MAX_K:
-            raise ValueError('K = %d keypoints outside [1, %d]' % (K, MAX_K))
-        self.K, self.tol, self.gauss, self.parts = K, check_tol(tol), _table(table), check_parts(parts, K)
+        self.K = check_keypoints(K)
+        self.tol, self.gauss, self.parts = check_tol(tol), _table(table), check_parts(parts, self.K)
         self.delta, self.floor, self.gamma = float(delta), float(floor), float(gamma)
-        self.device = torch.device(device)
-        if self.device.type != 'cuda':
-            raise RuntimeError(_NO_GPU)
-        if self.device.index is None:
-            self.device = torch.device('cuda', torch.cuda.current_device())
-        self._lib, self._C, self._torch = _lib.load(), C, torch
+        self.device = cuda_device(device, _NO_GPU)
+        self._lib = _lib.load()
         self._parts_dev = torch.from_numpy(self.parts).to(self.device)
         self._gauss_dev = torch.from_numpy(self.gauss).to(self.device)
         self._shape, self._bufs = None, None
 
-    def _stream(self):
-        return self._torch.cuda.current_stream(self.device).cuda_stream
+    _p = staticmethod(ptr)
 
-    def _p(self, t):
-        return None if t is None else self._C.c_void_p(t.data_ptr())
+    def _stream(self):
+        return stream(self.device)
 
     def buffers(self, B, L, R, T):
         """-> (work bytes, ticks (B, cap) int32, info (B, 2) int64, rows of the prediction and of the ground truth (R, 24) int64)"""
         if self._shape != (B, L, R, T):
-            torch = self._torch
+            import torch
             nbytes, cap = int(self._lib.sdt_sync_workspace_bytes(B, L, R, T)), int(self._lib.sdt_sync_onset_capacity(L))
             if nbytes < 0 or cap < 0:
                 raise ValueError('sizes outside the ranges: %d samples (at most 160 * 2^28), %d frames (at most 2^24)' % (L, T))
@@ -359,20 +352,15 @@ class _Device:
         return self._bufs
 
     def audio(self, x):
-        torch = self._torch
+        import torch
         if not torch.is_tensor(x) or x.device != self.device:
-            raise RuntimeError('the synchrony metrics take tensors on %s; %s' % (self.device, _NO_GPU))
+            raise RuntimeError('%s take tensors on %s; %s' % (_NOUN, self.device, _NO_GPU))
         if x.dtype != torch.float32 or x.ndim != 2 or x.shape[0] < 1:
             raise TypeError('audio must be (clips, samples) float32, got %s %s' % (tuple(x.shape), x.dtype))
         return x.detach().contiguous()
 
     def poses(self, x):
-        torch = self._torch
-        if not torch.is_tensor(x) or x.device != self.device:
-            raise RuntimeError('the synchrony metrics take tensors on %s; %s' % (self.device, _NO_GPU))
-        if x.dtype != torch.float64 or x.ndim != 4 or x.shape[2] != 2 or x.shape[3] != self.K or x.shape[0] < 1 or x.shape[1] < 1:
-            raise TypeError('poses must be (rows, frames, 2, %d) float64, got %s %s' % (self.K, tuple(x.shape), x.dtype))
-        return x.detach().contiguous()
+        return check_poses(x, self.K, self.device, _NOUN, _NO_GPU)
 
     def run_onsets(self, audio, bufs):
         from . import _lib
@@ -396,6 +384,8 @@ class SyncAccumulator(RecordTable):
     only call that waits for the device.  The state is one (num_clips + 1, 48) int64 tensor: the records, then a header row whose word 0
     counts the clip indices outside the table (``RecordTable`` owns it, ``state``, ``table``, ``reset``, ``result`` and ``result_words``)."""
 
+    NOUN, NO_GPU = _NOUN, _NO_GPU
+
     def __init__(self, num_clips, K, tol_ticks, sigma, device='cuda', parts=None):
         num_clips = check_num_clips(num_clips)
         self._dev = _Device(K, tol_ticks, gauss_table(sigma), device, parts)
@@ -406,23 +396,14 @@ class SyncAccumulator(RecordTable):
         """one validation step: rows (multiple * B, T, 2, K) of final poses, copy j of clip b in row j * B + b (``gt`` may be None); ``audio``
         (B, L) float32, or (multiple * B, L) as ``mutiply_batch`` leaves it: the first B rows are read, and so are the first B entries of the
         int64 ``clip_index``"""
+        import torch
         from . import _lib
-        d, torch, m = self._dev, self._dev._torch, int(multiple)
-        if not 1 <= m <= MAX_COPIES:
-            raise ValueError('%d copies outside [1, %d]' % (m, MAX_COPIES))
-        pred, gt = d.poses(pred), None if gt is None else d.poses(gt)
-        R, T = pred.shape[:2]
-        if (gt is not None and pred.shape != gt.shape) or R % m:
-            raise ValueError('prediction %s and ground truth %s must be %d copies of one batch' % (
-                tuple(pred.shape), None if gt is None else tuple(gt.shape), m))
-        B = R // m
+        d = self._dev
+        pred, gt, idx, B, R, T, m = self._step(pred, gt, clip_index, multiple, gt_optional=True)
         audio = d.audio(audio)
         if audio.shape[0] not in (B, R):
             raise ValueError('audio of %d clips for %d (or %d) rows' % (audio.shape[0], B, R))
         audio = audio[:B]
-        if not torch.is_tensor(clip_index) or clip_index.dtype != torch.int64 or clip_index.ndim != 1 or clip_index.numel() not in (B, R):
-            raise TypeError('clip_index must be an int64 tensor of %d (or %d) entries' % (B, R))
-        idx = clip_index[:B].to(self.device, non_blocking=True).contiguous()
         bufs = d.buffers(B, audio.shape[1], R, T)
         with torch.cuda.device(self.device):
             d.run_onsets(audio, bufs)

@@ -23,6 +23,7 @@ REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, REPO)
 
 from speechdrivestemplates_amd import augment as A  # noqa: E402
+from tools._timing import gpu_ms_alternating  # noqa: E402
 
 INNER = 10
 B, L, M, F = 32, 68266, 80, 427
@@ -31,26 +32,6 @@ OPTS = dict(seed=1234, gain_db=6.0, snr=(5.0, 30.0), noise_prob=1.0, shift_ms=50
 KEYS_ON = ["TRAIN.AUGMENT.ENABLE", True, "TRAIN.AUGMENT.SEED", 1234, "TRAIN.AUGMENT.GAIN_DB", 6.0, "TRAIN.AUGMENT.NOISE_SNR_DB", [5.0, 30.0],
            "TRAIN.AUGMENT.SHIFT_MS", 50.0, "TRAIN.AUGMENT.POLARITY", True, "TRAIN.AUGMENT.MEL_FREQ_MASKS", [2, 15],
            "TRAIN.AUGMENT.MEL_TIME_MASKS", [2, 40]]
-
-
-def gpu_ms_alternating(fns, reps, inner=INNER):
-    """per function the median and the minimum time of one call in ms: ``reps`` windows of ``inner`` back-to-back calls each, timed by HIP
-    events, the functions taking turns window by window (after three untimed calls of each)"""
-    for fn in fns:
-        for _ in range(3):
-            fn()
-    torch.cuda.synchronize()
-    times = [[] for _ in fns]
-    for _ in range(reps):
-        for fn, out in zip(fns, times):
-            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            a.record()
-            for _ in range(inner):
-                fn()
-            b.record()
-            b.synchronize()
-            out.append(a.elapsed_time(b) / inner)
-    return [(float(np.median(t)), float(np.min(t))) for t in times]
 
 
 def bench_kernels(reps):
@@ -74,7 +55,7 @@ def bench_kernels(reps):
                               lambda: A.augment_audio(x, clips, step, quiet, tables_q, ss, rec, y),
                               lambda: A.augment_audio(xa, clips, step, on, tables, ssa, rec, ya),
                               lambda: A.augment_audio(xa, clips, step, still, tables, ssa, rec, ya), lambda: A.mel_mask(mel, clips, step, on, rec),
-                              lambda: aug.audio(x, clips, step), lambda: dst.copy_(x)], reps)
+                              lambda: aug.audio(x, clips, step), lambda: dst.copy_(x)], reps, INNER)
     line = {"tool": "augment_bench", "case": "kernels", "device": torch.cuda.get_device_name(0), "reps": reps, "inner": INNER, "B": B, "L": L,
             "mel": [B, M, F], "options": {k: (list(v) if isinstance(v, tuple) else v) for k, v in OPTS.items()},
             "audio_bytes": 2 * B * L * 4, "launches": {"sumsq": 2, "audio": 2, "mel_mask": 2, "augmenter_audio": 4, "copy": 1}}

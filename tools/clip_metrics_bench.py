@@ -25,29 +25,10 @@ sys.path.insert(0, REPO)
 
 from speechdrivestemplates_amd import clip_metrics as cm  # noqa: E402
 from speechdrivestemplates_amd import ops  # noqa: E402
+from tools._timing import gpu_ms_alternating, host_ms  # noqa: E402
 
 INNER = 20  # calls between two events: one call is tens of microseconds, a window of one measures the event pair
 R, T, K, N_RESULT, N_VAL = 32, 64, 121, 4096, 256
-
-
-def gpu_ms_alternating(fns, reps):
-    """per function the median and the minimum time of one call in ms: ``reps`` windows of INNER back-to-back calls each, timed by HIP
-    events, the functions taking turns window by window (after three untimed calls of each)"""
-    for fn in fns:
-        for _ in range(3):
-            fn()
-    torch.cuda.synchronize()
-    times = [[] for _ in fns]
-    for _ in range(reps):
-        for fn, out in zip(fns, times):
-            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            a.record()
-            for _ in range(INNER):
-                fn()
-            b.record()
-            b.synchronize()
-            out.append(a.elapsed_time(b) / INNER)
-    return [(float(np.median(t)), float(np.min(t))) for t in times]
 
 
 def add_bytes(m):
@@ -71,7 +52,7 @@ def bench_add(reps):
     idx = {m: torch.arange(R // m, dtype=torch.int64, device="cuda") for m in (1, 4)}
     (a1, a1_min), (a4, a4_min), (fm, fm_min) = gpu_ms_alternating(
         [lambda: accs[1].add(p64, g64, idx[1], 1), lambda: accs[4].add(p64, g64, idx[4], 4),
-         lambda: ops.final_metrics(p32, g32, mean, std, scale, False, True)], reps)
+         lambda: ops.final_metrics(p32, g32, mean, std, scale, False, True)], reps, INNER)
     return [{"tool": "clip_metrics_bench", "case": "add", "device": torch.cuda.get_device_name(0), "reps": reps, "R": R, "T": T, "K": K, "copies": m,
              "launches": 3 if m == 1 else 4, "add_ms": ms, "add_min_ms": mn, "final_metrics_ms": fm, "final_metrics_min_ms": fm_min,
              "add_over_final_metrics": ms / fm, "bytes_moved": add_bytes(m), "gb_per_s": add_bytes(m) / ms / 1e6}
@@ -83,16 +64,10 @@ def bench_result(reps):
     rng = np.random.Generator(np.random.PCG64(4))
     gt = rng.uniform(0.0, 400.0, (N_RESULT, 3, 2, 5))
     acc.add(torch.from_numpy(gt + rng.standard_normal(gt.shape)).cuda(), torch.from_numpy(gt).cuda(), torch.arange(N_RESULT, dtype=torch.int64), 1)
-    acc.result()
-    times = []
-    for _ in range(max(reps, 5)):
-        torch.cuda.synchronize()
-        t = time.perf_counter()
-        res = acc.result()
-        times.append((time.perf_counter() - t) * 1e3)
-    assert res["clips_seen"] == N_RESULT
-    return {"tool": "clip_metrics_bench", "case": "result", "device": torch.cuda.get_device_name(0), "reps": len(times), "N": N_RESULT,
-            "result_ms": float(np.median(times)), "result_min_ms": float(np.min(times))}
+    ms, mn = host_ms(acc.result, reps)
+    assert acc.result()["clips_seen"] == N_RESULT
+    return {"tool": "clip_metrics_bench", "case": "result", "device": torch.cuda.get_device_name(0), "reps": max(reps, 5), "N": N_RESULT,
+            "result_ms": ms, "result_min_ms": mn}
 
 
 def bench_validate(reps):

@@ -24,27 +24,9 @@ import torch
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, REPO)
 
+from tools._timing import gpu_ms_alternating  # noqa: E402
+
 B, T, D, N_CLIPS = 32, 64, 32, 64
-
-
-def gpu_ms_alternating(fns, reps, inner):
-    """per function the median and the minimum time of one call in ms: ``reps`` windows of ``inner`` back-to-back calls each, timed by HIP
-    events, the functions taking turns window by window (after three untimed calls of each)"""
-    for fn in fns:
-        for _ in range(3):
-            fn()
-    torch.cuda.synchronize()
-    times = [[] for _ in fns]
-    for _ in range(reps):
-        for fn, out in zip(fns, times):
-            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            a.record()
-            for _ in range(inner):
-                fn()
-            b.record()
-            b.synchronize()
-            out.append(a.elapsed_time(b) / inner)
-    return [(float(np.median(t)), float(np.min(t))) for t in times]
 
 
 def pipeline():

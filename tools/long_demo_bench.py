@@ -22,29 +22,10 @@ REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, REPO)
 
 from speechdrivestemplates_amd import long_demo as ld  # noqa: E402
+from tools._timing import gpu_ms_alternating  # noqa: E402
 
 INNER = 10
 F, W, O, K, SMOOTH, BATCH = 4500, 64, 16, 121, (2, 2), 32
-
-
-def gpu_ms_alternating(fns, reps, inner=INNER):
-    """per function the median and the minimum time of one call in ms: ``reps`` windows of ``inner`` back-to-back calls each, timed by HIP
-    events, the functions taking turns window by window (after three untimed calls of each)"""
-    for fn in fns:
-        for _ in range(3 if inner > 1 else 1):
-            fn()
-    torch.cuda.synchronize()
-    times = [[] for _ in fns]
-    for _ in range(reps):
-        for fn, out in zip(fns, times):
-            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            a.record()
-            for _ in range(inner):
-                fn()
-            b.record()
-            b.synchronize()
-            out.append(a.elapsed_time(b) / inner)
-    return [(float(np.median(t)), float(np.min(t))) for t in times]
 
 
 def bench_kernels(reps):
@@ -63,7 +44,7 @@ def bench_kernels(reps):
 
     names = ("stitch", "smooth", "report", "stitch_smooth_report")
     res = gpu_ms_alternating([lambda: ld.stitch(win, O, F), lambda: ld.smooth(stitched, SMOOTH), lambda: ld.report(win, stitched, smoothed, O),
-                              all_three], reps)
+                              all_three], reps, INNER)
     pose_bytes = F * 2 * K * 8
     moved = {"stitch": N * W * 2 * K * 8 + pose_bytes, "smooth": 2 * pose_bytes}  # (report re-reads neighbouring frames: not stated)
     line = {"tool": "long_demo_bench", "case": "kernels", "device": torch.cuda.get_device_name(0), "reps": reps, "inner": INNER, "F": F, "W": W,
@@ -74,7 +55,7 @@ def bench_kernels(reps):
             line[name + "_bytes"] = moved[name]
     audio = torch.from_numpy(rng.standard_normal(F * 16000 // 15).astype(np.float32)).cuda()
     offs = torch.tensor(offsets[:BATCH], dtype=torch.int64, device="cuda")
-    (g_ms, g_min), = gpu_ms_alternating([lambda: ld.gather_windows(audio, offs, 68266)], reps)
+    (g_ms, g_min), = gpu_ms_alternating([lambda: ld.gather_windows(audio, offs, 68266)], reps, INNER)
     gather = {"tool": "long_demo_bench", "case": "gather", "device": torch.cuda.get_device_name(0), "reps": reps, "inner": INNER, "windows": BATCH,
               "Lw": 68266, "L": int(audio.numel()), "gather_ms": g_ms, "gather_min_ms": g_min, "gather_bytes": 2 * BATCH * 68266 * 4}
     return [line, gather]
@@ -103,7 +84,7 @@ def bench_run(reps):
 
     with torch.no_grad():
         pipe.apply_knobs()
-        (gen, gen_min), (whole, whole_min) = gpu_ms_alternating([lambda: runner.generate(batch), run], max(3, reps // 4), inner=1)
+        (gen, gen_min), (whole, whole_min) = gpu_ms_alternating([lambda: runner.generate(batch), run], max(3, reps // 4), 1, warmup=1)
     res = out["res"]
     assert res["poses_pred_batch"].shape == (1, F, 2, K) and bool(torch.isfinite(res["poses_pred_batch"]).all())
     pipe.close()

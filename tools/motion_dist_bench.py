@@ -13,7 +13,6 @@ import argparse
 import json
 import os
 import sys
-import time
 
 import numpy as np
 import torch
@@ -23,29 +22,10 @@ sys.path.insert(0, REPO)
 
 from speechdrivestemplates_amd import clip_metrics as cm  # noqa: E402
 from speechdrivestemplates_amd import motion_dist as md  # noqa: E402
+from tools._timing import gpu_ms_alternating, host_ms  # noqa: E402
 
 INNER = 20  # calls between two events: one call is tens of microseconds, a window of one measures the event pair
 R, T, K, N_RESULT = 32, 64, 121, 4096
-
-
-def gpu_ms_alternating(fns, reps):
-    """per function the median and the minimum time of one call in ms: ``reps`` windows of INNER back-to-back calls each, timed by HIP
-    events, the functions taking turns window by window (after three untimed calls of each)"""
-    for fn in fns:
-        for _ in range(3):
-            fn()
-    torch.cuda.synchronize()
-    times = [[] for _ in fns]
-    for _ in range(reps):
-        for fn, out in zip(fns, times):
-            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            a.record()
-            for _ in range(INNER):
-                fn()
-            b.record()
-            b.synchronize()
-            out.append(a.elapsed_time(b) / INNER)
-    return [(float(np.median(t)), float(np.min(t))) for t in times]
 
 
 def add_bytes(m):
@@ -63,22 +43,11 @@ def bench_add(reps):
         acc = md.MotionDistAccumulator(R // m, K, None, "cuda")
         ref = cm.ClipMetricsAccumulator(R // m, K, [0.1, 0.2], "cuda")
         idx = torch.arange(R // m, dtype=torch.int64, device="cuda")
-        (ms, mn), (cms, cmn) = gpu_ms_alternating([lambda: acc.add(p64, g64, idx, m), lambda: ref.add(p64, g64, idx, m)], reps)
+        (ms, mn), (cms, cmn) = gpu_ms_alternating([lambda: acc.add(p64, g64, idx, m), lambda: ref.add(p64, g64, idx, m)], reps, INNER)
         lines.append({"tool": "motion_dist_bench", "case": "add", "device": torch.cuda.get_device_name(0), "reps": reps, "R": R, "T": T, "K": K,
                       "copies": m, "launches": 2, "add_ms": ms, "add_min_ms": mn, "clip_metrics_add_ms": cms, "clip_metrics_add_min_ms": cmn,
                       "add_over_clip_metrics_add": ms / cms, "bytes_moved": add_bytes(m), "gb_per_s": add_bytes(m) / ms / 1e6})
     return lines
-
-
-def host_ms(fn, reps):
-    fn()
-    times = []
-    for _ in range(max(reps, 5)):
-        torch.cuda.synchronize()
-        t = time.perf_counter()
-        fn()
-        times.append((time.perf_counter() - t) * 1e3)
-    return float(np.median(times)), float(np.min(times))
 
 
 def bench_result(reps):

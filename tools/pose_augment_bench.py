@@ -21,7 +21,8 @@ REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, REPO)
 
 from speechdrivestemplates_amd import pose_augment as PA  # noqa: E402
-from tools.augment_bench import INNER, gpu_ms_alternating  # noqa: E402
+from tools._timing import gpu_ms_alternating  # noqa: E402
+from tools.augment_bench import INNER  # noqa: E402
 
 B, T, K = 32, 64, 121
 OPTS = dict(seed=1234, mirror_prob=0.5, scale_pct=10.0, rot_deg=15.0)
@@ -49,7 +50,7 @@ def bench_kernels(reps):
 
     names = ("augment", "mirror_only", "identity", "augment_no_score", "augmenter", "copy")
     res = gpu_ms_alternating([call("augment"), call("mirror_only"), call("identity"), call("augment", False),
-                              lambda: aug(poses, score, mean, std, clips, step), lambda: dst.copy_(poses)], reps)
+                              lambda: aug(poses, score, mean, std, clips, step), lambda: dst.copy_(poses)], reps, INNER)
     line = {"tool": "pose_augment_bench", "case": "kernels", "device": torch.cuda.get_device_name(0), "reps": reps, "inner": INNER, "B": B, "T": T,
             "K": K, "options": OPTS, "pose_bytes": 2 * B * T * 2 * K * 4, "launches": {"augment": 2, "augmenter": 2, "copy": 1}}
     for name, (ms, mn) in zip(names, res):

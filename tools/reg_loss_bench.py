@@ -26,30 +26,11 @@ sys.path.insert(0, REPO)
 
 from speechdrivestemplates_amd import _lib, ops  # noqa: E402
 from speechdrivestemplates_amd.core.datasets.gesture_dataset import PoseTransforms  # noqa: E402
+from tools._timing import gpu_ms_alternating  # noqa: E402
 
 INNER = 20  # calls between two events: one call is tens of microseconds, a window of one measures the event pair
 B, T, K = 32, 64, 121
 LAM_REG, LAM_VEL, MIN_CONF, PARTS = 1.0, 0.5, 0.3, (1.0, 0.5, 2.0)
-
-
-def gpu_ms_alternating(fns, reps):
-    """per function the median and the minimum time of one call in ms: ``reps`` windows of INNER back-to-back calls each, timed by HIP
-    events, the functions taking turns window by window (after three untimed calls of each)"""
-    for fn in fns:
-        for _ in range(3):
-            fn()
-    torch.cuda.synchronize()
-    times = [[] for _ in fns]
-    for _ in range(reps):
-        for fn, out in zip(fns, times):
-            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            a.record()
-            for _ in range(INNER):
-                fn()
-            b.record()
-            b.synchronize()
-            out.append(a.elapsed_time(b) / INNER)
-    return [(float(np.median(t)), float(np.min(t))) for t in times]
 
 
 def main(argv=None):
@@ -103,7 +84,7 @@ def main(argv=None):
         _lib.check(lib.sdt_l1_loss_bwd_f32(p_, g_, one.data_ptr(), n, LAM_REG, dp.data_ptr(), st))
 
     names = ["fused", "l1", "composed", "fused_raw", "l1_raw"]
-    res = dict(zip(names, gpu_ms_alternating([fused, l1, composed, fused_raw, l1_raw], a.reps)))
+    res = dict(zip(names, gpu_ms_alternating([fused, l1, composed, fused_raw, l1_raw], a.reps, INNER)))
     common = {"tool": "reg_loss_bench", "device": torch.cuda.get_device_name(0), "reps": a.reps, "inner": INNER, "B": B, "T": T, "C": C,
               "elements": n, "traffic_mb": 4 * n * 4 / 1e6}  # forward reads pred, gt, score; backward reads them again and writes dpred
     lines = []

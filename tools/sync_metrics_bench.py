@@ -22,29 +22,10 @@ sys.path.insert(0, REPO)
 from speechdrivestemplates_amd import clip_metrics as cm  # noqa: E402
 from speechdrivestemplates_amd import long_demo as ld  # noqa: E402
 from speechdrivestemplates_amd import sync_metrics as sm  # noqa: E402
+from tools._timing import gpu_ms_alternating  # noqa: E402
 
 INNER = 20  # calls between two events: one call is tens of microseconds, a window of one measures the event pair
 R, T, K, L, F, L_LONG, W, O = 32, 64, 121, 68266, 4500, 4800000, 64, 0
-
-
-def gpu_ms_alternating(fns, reps, inner=INNER):
-    """per function the median and the minimum time of one call in ms: ``reps`` windows of ``inner`` back-to-back calls each, timed by HIP
-    events, the functions taking turns window by window (after three untimed calls of each)"""
-    for fn in fns:
-        for _ in range(3):
-            fn()
-    torch.cuda.synchronize()
-    times = [[] for _ in fns]
-    for _ in range(reps):
-        for fn, out in zip(fns, times):
-            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            a.record()
-            for _ in range(inner):
-                fn()
-            b.record()
-            b.synchronize()
-            out.append(a.elapsed_time(b) / inner)
-    return [(float(np.median(t)), float(np.min(t))) for t in times]
 
 
 def speech(n, rng):
@@ -64,7 +45,7 @@ def bench_add(reps):
     clip = {m: cm.ClipMetricsAccumulator(R // m, K, [0.1, 0.2], "cuda") for m in (1, 4)}
     idx = {m: torch.arange(R // m, dtype=torch.int64, device="cuda") for m in (1, 4)}
     res = gpu_ms_alternating([lambda: sync[1].add(p64, g64, audio, idx[1], 1), lambda: sync[4].add(p64, g64, audio[:R // 4], idx[4], 4),
-                              lambda: clip[1].add(p64, g64, idx[1], 1), lambda: clip[4].add(p64, g64, idx[4], 4)], reps)
+                              lambda: clip[1].add(p64, g64, idx[1], 1), lambda: clip[4].add(p64, g64, idx[4], 4)], reps, INNER)
     onsets = int(sync[1].table()[:, sm.ONSETS].sum())
     return [{"tool": "sync_metrics_bench", "case": "add", "device": torch.cuda.get_device_name(0), "reps": reps, "R": R, "T": T, "K": K, "L": L,
              "copies": m, "launches": 7, "onsets_in_the_batch": onsets if m == 1 else None, "add_ms": res[i][0], "add_min_ms": res[i][1],

@@ -24,29 +24,10 @@ sys.path.insert(0, REPO)
 
 from speechdrivestemplates_amd import ops  # noqa: E402
 from speechdrivestemplates_amd import tensor_hist as th  # noqa: E402
+from tools._timing import gpu_ms_alternating  # noqa: E402
 
 
 INNER = 20  # calls between two events: one call is tens of microseconds, a window of one measures the event pair
-
-
-def gpu_ms_alternating(fns, reps):
-    """per function the median and the minimum time of one call in ms: ``reps`` windows of INNER back-to-back calls each, timed by HIP
-    events, the functions taking turns window by window (after three untimed calls of each)"""
-    for fn in fns:
-        for _ in range(3):
-            fn()
-    torch.cuda.synchronize()
-    times = [[] for _ in fns]
-    for _ in range(reps):
-        for fn, out in zip(fns, times):
-            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            a.record()
-            for _ in range(INNER):
-                fn()
-            b.record()
-            b.synchronize()
-            out.append(a.elapsed_time(b) / INNER)
-    return [(float(np.median(t)), float(np.min(t))) for t in times]
 
 
 def host_route(flat, offsets, sizes):
@@ -62,7 +43,7 @@ def host_route(flat, offsets, sizes):
 def bench(name, flat, offsets, sizes, reps, host):
     partial = torch.zeros(ops.grad_sumsq_partials(), device=flat.device, dtype=torch.float64)
     (snap, snap_min), (sumsq, sumsq_min) = gpu_ms_alternating([lambda: th.flat_histograms(flat, offsets, sizes),
-                                                               lambda: ops.grad_sumsq(flat, partial)], reps)
+                                                               lambda: ops.grad_sumsq(flat, partial)], reps, INNER)
     counts, tallies, stats = (t.cpu().numpy() for t in th.flat_histograms(flat, offsets, sizes))
     line = {"tool": "tensor_hist_bench", "case": name, "device": torch.cuda.get_device_name(0), "reps": reps, "elements": int(sum(sizes)),
             "segments": len(sizes), "chunks": int(sum(-(-n // th.HIST_CHUNK) for n in sizes)), "buffer_mb": flat.numel() * 4 / 1e6,
