@@ -615,6 +615,9 @@ def check_streamk():
 # Measured +1.3 % over the 14 forward / input-gradient launches (profiles/r06_korder_ab.txt) -- inside the box-to-box spread of the step, and it
 # regroups every Conv2d sum: trajectory quantities behind an Adam step move past their CALIBRATED bounds (tests/golden/margins.json; e.g. sdt_bp
 # step-1 lip_sync 7e-7 -> 2e-5 against a stated 1e-3).  Not worth re-recording 800 margins in the round that had to turn the suite green: off.
+# Its results ARE checked: tests/test_k_order_conv_sweep_gpu.py runs order 1 over every cursor edge of the loader (range cuts inside a chunk, culled
+# and rotated tap masks, mixed parity classes, one tap, one chunk, reserved slots, pre-split planes) -- exact on integer operands, at the sweeps' own
+# float64 bars on random ones, bf16 and split-fp32.  What remains before a default-on is the re-recording of the trajectory margins, nothing else.
 SK_K_ORDER = 0
 _K_ORDER_SET = [None]
 

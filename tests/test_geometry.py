@@ -216,6 +216,12 @@ def _plan_tables(ops, garr, n, rpg, bwd_groups, reserve=0):
         assert lib.sdt_convsk_plan_build(garr, n, rpg, bwd_groups, ctypes.addressof(blob), nbytes) == 0, lib.sdt_last_error()
     finally:
         lib.sdt_convsk_set_reserved_slots(0)
+    return _read_plan(blob)[:5]
+
+
+def _read_plan(blob):
+    """Header and tables of a plan blob (csrc/convsk.hip plan_build; also the ``host`` copy of an ops._SKPlan), plus the class table: one row of
+    SK_CLS_INTS ints per class -- Hi, Wi, Cin, Cout, ntaps, nkc, tile_begin, nmb, row_begin, mt_begin, Tw, then the tap shifts."""
     P = np.frombuffer(blob, dtype=np.int32).copy()
     hdr = dict(bm=int(P[1]), bn=int(P[2]), G=int(P[3] & 0xffff), wpc=int(P[3] >> 16), ncls=int(P[4]), nnb=int(P[5] & 0xffff), ntmajor=int(P[5] >> 16),
                T=int(P[6]), S=int(P[7]), rows=int(P[8]), mts=int(P[9]))
@@ -223,7 +229,8 @@ def _plan_tables(ops, garr, n, rpg, bwd_groups, reserve=0):
     tileinfo = P[P[11]:P[11] + 2 * hdr["mts"]].reshape(-1, 2)
     tilecum = P[P[12]:P[12] + hdr["T"] + 1]
     range_tile = P[P[13]:P[13] + hdr["G"]]
-    return hdr, rowinfo, tileinfo, tilecum, range_tile
+    classes = P[P[14]:P[15]].reshape(hdr["ncls"], -1)
+    return hdr, rowinfo, tileinfo, tilecum, range_tile, classes
 
 
 @pytest.mark.parametrize("case", [("3x3 pad 1, 10-row images (row-major, n-tile-major)", 32, 10, 53, 256, 256, 3, 3, 1, 1, "fwd", 0),
