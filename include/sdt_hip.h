@@ -1176,6 +1176,59 @@ int sdt_code_fit_set_f32(const float* codes, float* h, int B, int T, int C, int 
 int sdt_code_fit_pick_f32(const double* cand_loss, int M, int B, const float* cands, int D, int32_t* index, double* best, float* code_out,
                           void* stream);
 
+/*
+ * Precision / recall and density / coverage between the pose-encoder features of the real and of the generated clips (TEST.PRDC;
+ * speechdrivestemplates_amd/prdc.py; DESIGN.md section 33 is the contract, prdc.prdc_model / commit_model / gather_model are the same
+ * operations in numpy; no counterpart in the reference).  Rows are float64 vectors of D columns, float32 features widened exactly.
+ * d2(x, y) = the sum over c = 0 .. D-1 in that order from +0.0 of (x_c - y_c)^2, every subtract, multiply and add rounded on its own
+ * (csrc/exact_f64.h): symmetric to the bit.  The radius of a row in its set = the k-th smallest d2 to the OTHER rows of the set (self left
+ * out by position, so duplicates at d2 = 0 count), +inf in a set of at most k rows.  No square root, no floating-point atomics, no
+ * allocation, no host synchronisation; every pointer except ``tables`` (a host array, read during the call) is a device buffer.  Sizes are
+ * checked before any launch: rows (and clips x copies) 1 .. 2^20 per set, D 1 .. 64, k 1 .. 16, copies 1 .. 16, slices 1 .. 4096; anything
+ * else returns SDT_ERR_UNSUPPORTED (a null pointer or a workspace that is too small SDT_ERR_ARG).
+ *   A record is sdt_prdc_cols(D, m) = SDT_PRDC_HEADER_WORDS + D (1 + m) words of 8 bytes: int64 0 copies m (0 = no step has committed the
+ *     clip: the seen word), 1 nonfinite (a NaN or an infinity among the clip's features); float64 [2, 2 + D) the ground truth of copy 0, mu then
+ *     logvar (D = 2 Dh); [2 + D (1 + j), 2 + D (2 + j)) the prediction of copy j.  A table is (N + 1) records: row N is the header, whose word 0
+ *     counts the clip indices outside [0, N) (they write nothing else).
+ *   commit: mu_pred, logvar_pred, mu_gt, logvar_gt (m B, Dh) float32, copy j of clip b in row j B + b -> row clip_index[b] of table.
+ *   gather: tables are ranks (1..64) table pointers; clip n takes the record of the lowest rank with copies != 0; records with nonfinite set
+ *     are left out of both sets and counted.  Live clip number p (its position among the live clips in index order, an exclusive prefix over
+ *     the live flags) gives row p of real (its ground truth) and rows p m + j of gen (its predictions), the leading dim_used columns of each,
+ *     pitch dim_used; real_clip / gen_clip / gen_copy map a row back.  With floor_pass the ground truth of live clip p gives row p / 2 of real
+ *     for an even p and row p / 2 of gen for an odd p (gen_copy 0).  real holds N rows, gen N m; work 2 N words.  counts (8 int64): 0 rows of
+ *     real, 1 rows of gen, 2 clips with a record, 3 of them left out as nonfinite, 4 index errors of all tables, 5 live clips, 6, 7 zero.
+ *   The all-pairs stages read their row counts from device words (count, qcount, scount: at most cap rows are ever touched), so no stage
+ *   waits for the host.  One thread owns a query row, the other set streams through LDS in tiles of 32 rows, the streamed range is split
+ *   into ``slices`` equal stretches (gridDim.y; sdt_prdc_slices proposes a number) whose partial results a second launch merges: the
+ *   results do not depend on the number of slices.
+ *   knn: radius[i] of every row of x (count rows of D) as defined above.  part: slices x cap x 16 words.
+ *   cross: for every row i of q: ball_count[i] = the number of rows s of sx with d2(q_i, sx_s) <= s_radius[s]; nearest_d2[i] = the smallest
+ *     d2(q_i, sx_s) (+inf for an empty sx) and nearest[i] = the lowest s that has it (-1).  part: slices x qcap x 3 words.
+ *   reduce: counts as gather leaves them (words 0 .. 4 are read); r_real the radii of real; gen_balls of cross(gen, real, r_real); real_balls
+ *     and real_nearest_d2 of cross(real, gen, r_gen).  covered[i] = real_nearest_d2[i] <= r_real[i], recalled[i] = real_balls[i] > 0.  out
+ *     (SDT_PRDC_OUT_WORDS = 16): float64 0 precision = #{j : gen_balls[j] > 0} / Ng, 1 recall = #recalled / Nr, 2 density = sum_j gen_balls[j]
+ *     / (k Ng), 3 coverage = #covered / Nr, each one division of two exactly converted integers, each the NaN 0x7ff8000000000000 when err != 0;
+ *     int64 4 .. 7 the four numerators, 8 Nr, 9 Ng, 10 k, 11 err (SDT_PRDC_ERR_REAL_ROWS: Nr <= k, SDT_PRDC_ERR_GEN_ROWS: Ng <= k),
+ *     12 clips with a record, 13 left out as nonfinite, 14 index errors, 15 zero.
+ */
+#define SDT_PRDC_HEADER_WORDS 2
+#define SDT_PRDC_OUT_WORDS 16
+#define SDT_PRDC_ERR_REAL_ROWS 1
+#define SDT_PRDC_ERR_GEN_ROWS 2
+int64_t sdt_prdc_cols(int D, int m);
+int sdt_prdc_commit(const float* mu_pred, const float* logvar_pred, const float* mu_gt, const float* logvar_gt, const int64_t* clip_index, int B,
+                    int m, int Dh, void* table, int64_t N, void* stream);
+int sdt_prdc_gather(const void* const* tables, int ranks, int64_t N, int D, int m, int dim_used, int floor_pass, void* work, double* real,
+                    double* gen, int64_t* real_clip, int64_t* gen_clip, int64_t* gen_copy, int64_t* counts, void* stream);
+int64_t sdt_prdc_slices(int64_t queries, int64_t streamed);
+int sdt_prdc_knn(const double* x, const int64_t* count, int64_t cap, int D, int k, int slices, void* part, int64_t part_words, double* radius,
+                 void* stream);
+int sdt_prdc_cross(const double* q, const int64_t* qcount, int64_t qcap, const double* sx, const int64_t* scount, int64_t scap,
+                   const double* s_radius, int D, int slices, void* part, int64_t part_words, int64_t* ball_count, int64_t* nearest,
+                   double* nearest_d2, void* stream);
+int sdt_prdc_reduce(const int64_t* counts, int64_t real_cap, int64_t gen_cap, int k, const double* r_real, const int64_t* gen_balls,
+                    const int64_t* real_balls, const double* real_nearest_d2, int64_t* covered, int64_t* recalled, int64_t* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

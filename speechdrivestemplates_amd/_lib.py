@@ -222,6 +222,13 @@ SIGNATURES = {
     "sdt_code_fit_step_f32": [_p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, C.c_double, _f, _f, _f, _p, _i, _i, _i, _i, _p, _i64, _p, _i, _p],
     "sdt_code_fit_set_f32": [_p, _p, _i, _i, _i, _i, _p],
     "sdt_code_fit_pick_f32": [_p, _i, _i, _p, _i, _p, _p, _p, _p],
+    "sdt_prdc_cols": [_i, _i],  # (the two size functions return int64_t: restype set in load())
+    "sdt_prdc_slices": [_i64, _i64],
+    "sdt_prdc_commit": [_p, _p, _p, _p, _p, _i, _i, _i, _p, _i64, _p],
+    "sdt_prdc_gather": [C.POINTER(C.c_void_p), _i, _i64, _i, _i, _i, _i, _p, _p, _p, _p, _p, _p, _p, _p],
+    "sdt_prdc_knn": [_p, _p, _i64, _i, _i, _i, _p, _i64, _p, _p],
+    "sdt_prdc_cross": [_p, _p, _i64, _p, _p, _i64, _p, _i, _i, _p, _i64, _p, _p, _p, _p],
+    "sdt_prdc_reduce": [_p, _i64, _i64, _i, _p, _p, _p, _p, _p, _p, _p, _p],
 }
 F32, BF16 = 0, 1  # enum sdt_dtype
 
@@ -288,6 +295,8 @@ def load():
     lib.sdt_sync_workspace_bytes.restype = C.c_int64
     lib.sdt_augment_workspace_bytes.restype = C.c_int64
     lib.sdt_motion_dist_epoch_work_words.restype = C.c_int64
+    lib.sdt_prdc_cols.restype = C.c_int64
+    lib.sdt_prdc_slices.restype = C.c_int64
     for name in ("threads", "chunk", "buckets", "max_segments"):
         getattr(lib, "sdt_tensor_hist_" + name).restype = C.c_int64
     lib.sdt_conv_dw_group_plan_bytes.argtypes = [_i]

@@ -4,7 +4,8 @@ csrc/record_table.h is the device side).
 A table is a (num_clips + 1, cols) int64 tensor: one record per clip of the validation set, then a header row whose word 0 counts the clip
 indices outside the table.  Under data parallelism there is one table per rank; per clip the lowest rank whose record has its seen word set
 gives the record.  The epoch sum runs over chunks of 64 clips in index order, then over the chunk partials in order.  The word layouts, what
-each word adds up and the final divisions belong to the families."""
+each word adds up and the final divisions belong to the families.  prdc.FeatureSetAccumulator keeps its feature table under the same protocol
+(its epoch stage compares sets of clips instead of summing over them)."""
 import numpy as np
 
 from ._exact_model import MAX_COPIES, MAX_K, MAX_TABLES
@@ -139,11 +140,10 @@ class RecordTable:
         int64 tensor (or a list of such states / accumulators), one entry per rank; the lowest rank that has seen a clip gives its record"""
         return self.epoch_values(self.result_words(gathered))
 
-    def result_words(self, gathered=None):
-        """the words of the epoch vector as a numpy int64 array (float64 words viewed as int64)"""
+    def table_pointers(self, gathered=None):
+        """-> (a host array of table pointers, their number, the tensors that own them): this accumulator's state, or the checked ``gathered``"""
         import ctypes as C
         import torch
-        from . import _lib
         if gathered is None:
             blocks = [self._state]
         elif torch.is_tensor(gathered):
@@ -155,7 +155,13 @@ class RecordTable:
         for b in blocks:
             if b.dtype != torch.int64 or tuple(b.shape) != tuple(self._state.shape) or b.device != self.device or not b.is_contiguous():
                 raise ValueError('a gathered state must be a contiguous %s int64 tensor on %s' % (tuple(self._state.shape), self.device))
-        ptrs = (C.c_void_p * len(blocks))(*[b.data_ptr() for b in blocks])
+        return (C.c_void_p * len(blocks))(*[b.data_ptr() for b in blocks]), len(blocks), blocks
+
+    def result_words(self, gathered=None):
+        """the words of the epoch vector as a numpy int64 array (float64 words viewed as int64)"""
+        import torch
+        from . import _lib
+        ptrs, ranks, _keep = self.table_pointers(gathered)
         with torch.cuda.device(self.device):
-            _lib.check(self._launch_epoch(ptrs, len(blocks), self._stream()))
+            _lib.check(self._launch_epoch(ptrs, ranks, self._stream()))
             return self._out.cpu().numpy()  # (same stream: ordered after the kernels, and the one wait of an accumulator)

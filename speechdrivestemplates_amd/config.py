@@ -130,7 +130,23 @@ _DEFAULTS = {
              # with the table's per-dimension mean and unbiased variance.  STEPS (1 .. 1000) and LR (> 0) are UNTUNED defaults: nobody has
              # yet looked for the pair that converges fastest on a trained model.  CANDIDATES 0 .. 64.  False = the loop as it was, no
              # kernel of the fit is launched.
-             "FIT_CODE": {"ENABLE": False, "STEPS": 100, "LR": 0.05, "INIT": "mean", "CANDIDATES": 0, "PRIOR": 0.0}},
+             "FIT_CODE": {"ENABLE": False, "STEPS": 100, "LR": 0.05, "INIT": "mean", "CANDIDATES": 0, "PRIOR": 0.0},
+             # extension (precision / recall / density / coverage of the generated gestures, prdc.FeatureSetAccumulator / csrc/prdc.hip;
+             # DESIGN.md section 33; Voice2Pose with VOICE2POSE.POSE_ENCODER.NAME only; MULTIPLE 1 .. 16).  ENABLE True = every test_step
+             # also commits its clips' pose-encoder features (mu ++ logvar of the ground truth and of every MULTIPLE copy of the prediction)
+             # to a table on the GPU, and validate() / test() compare the SET of generated clips with the SET of real clips in the feature
+             # space of the FGD: precision (the share of generated rows inside the k-nearest-neighbour ball of some real row: are the
+             # gestures plausible?), recall (the share of real rows inside the ball of some generated row: are all templates covered?),
+             # density and coverage (their outlier-robust forms).  Sixteen values: precision_mu, recall_mu, density_mu, coverage_mu on the
+             # mu columns, the same four with _mu_logvar on all columns, and each of the eight again with _floor = the same metric between
+             # the real clips at even and at odd positions of the index-ordered list (what two halves of the real data score at this set
+             # size; NaN when a half has at most K rows); prdc_clips_nonfinite counts the clips left out for a NaN / inf feature.  Over the
+             # tables of ALL ranks (one all-gather), the same bits on every rank.  With SAVE_NPZ the master also writes
+             # results/epoch<E>-<TAG>-prdc.npz (per-row radii, ball counts, nearest real clip, flags, clip indices).  False = the loop as it
+             # was, nothing constructed or launched.  K: neighbours of a radius, an integer 1 .. 16; 5 is the value of the density /
+             # coverage paper and UNTUNED for validation sets of a few hundred clips.  Not verified: real data, a trained encoder, a
+             # multi-GPU run.
+             "PRDC": {"ENABLE": False, "K": 5}},
     "DEMO": {"MULTIPLE": 1, "NUM_SAMPLES": 1, "CODE_INDEX": None, "CODE_INDEX_B": None, "CODE_PATH": None,
              # extensions (the whole-recording demo, long_demo.LongDemo / csrc/long_demo.hip; Voice2Pose only).
              # LONG_FORM True = a demo input of F >= DATASET.NUM_FRAMES frames is generated as overlapping windows of NUM_FRAMES frames (the
@@ -427,6 +443,22 @@ def check_motion_dist(cfg):
         return None
     _check_clip_table_key(cfg, "TEST.MOTION_DIST", "motion histograms of predicted gestures against the ground truth")
     return {'edges': edges}
+
+
+def check_prdc(cfg):
+    """Validate TEST.PRDC (ValueError names the key; K is checked whether or not the key is on).  Returns None with ENABLE off, else
+    {'k'} as a Python value (prdc.FeatureSetAccumulator's k)."""
+    on, k = cfg.TEST.PRDC.ENABLE, cfg.TEST.PRDC.K
+    if not isinstance(on, bool):
+        raise ValueError("TEST.PRDC.ENABLE must be True or False, got %r" % (on,))
+    if not _is_int(k) or not 1 <= k <= 16:
+        raise ValueError("TEST.PRDC.K must be an integer from 1 to 16, got %r" % (k,))
+    if not on:
+        return None
+    _check_clip_table_key(cfg, "TEST.PRDC.ENABLE", "precision / recall / density / coverage of the generated gestures' pose-encoder features")
+    if cfg.VOICE2POSE.POSE_ENCODER.NAME is None:
+        raise ValueError("TEST.PRDC.ENABLE needs VOICE2POSE.POSE_ENCODER.NAME (the features are the pose encoder's mu and logvar), got None")
+    return {'k': int(k)}
 
 
 def check_augment(cfg):

@@ -11,7 +11,7 @@ from types import SimpleNamespace
 
 import torch
 
-from ... import clip_metrics, motion_dist, ops, sync_metrics
+from ... import clip_metrics, motion_dist, ops, prdc, sync_metrics
 from ..datasets.gesture_dataset import PoseTransforms
 
 
@@ -95,6 +95,44 @@ class ClipTable(_Observer):
             module.save_table('%s/epoch%d-%s-%s_metrics.npz' % (d, epoch, tag, self.label), module.merge_tables([t.cpu().numpy() for t in tables]),
                               *self.save_args())
         return {k + self.suffix: v for k, v in res.items() if k not in module.BOOKKEEPING}
+
+
+class FeatureSets(ClipTable):
+    """TEST.PRDC: precision / recall / density / coverage between the set of generated and the set of real pose-encoder features (prdc.py)"""
+    key = ('TEST', 'PRDC')
+
+    def enabled(self, cfg):
+        return bool(cfg.TEST.PRDC.ENABLE)
+
+    def step(self, ctx):
+        r = ctx.results
+        ops.join_side_stream()  # (the features come from the side stream, as in DeviceFGD.step)
+        if self.acc is None or self.acc.copies != ctx.multiple:  # (a record is laid out for its number of copies)
+            from ...config import check_prdc
+            self.acc = prdc.FeatureSetAccumulator(self.num_clips(), 2 * r['mu_pred'].shape[1], ctx.multiple,
+                                                  check_prdc(self.pipe.cfg)['k'], r['mu_pred'].device)
+        self.acc.add(r['mu_pred'], r['logvar_pred'], r['mu_gt'], r['logvar_gt'], ctx.batch['clip_index'])
+
+    def epoch(self, epoch, tag):
+        """the sixteen values over the clips every rank delivered (the mu columns, then all columns; each with its floor) and
+        prdc_clips_nonfinite: the same bits on every rank.  Too few clips for K is a warning and NaN values, not the end of a training run."""
+        acc, pipe = self.acc, self.pipe
+        if acc is None:  # no validation step ran
+            return {}
+        gathered = gather_states(pipe.cfg, acc.state())
+        out, res = {}, None
+        for sfx, dim_used in (('_mu', acc.dim // 2), ('_mu_logvar', acc.dim)):
+            res = acc.result(dim_used=dim_used, gathered=gathered)
+            out.update({v + sfx + floor: res[v + floor] for floor in ('', '_floor') for v in prdc.VALUES})
+        if res['clips_nonfinite'] or res['index_errors']:
+            logging.warning('[VAL] feature-set metrics: %d clip(s) left out for a non-finite feature, %d clip index(es) outside the table of %d'
+                            % (res['clips_nonfinite'], res['index_errors'], acc.num_clips))
+        if pipe.is_master_process() and pipe.cfg.TEST.SAVE_NPZ and pipe.base_path is not None:  # (the rows of the last result: all columns)
+            d = os.path.join(pipe.base_path, 'results')
+            os.makedirs(d, exist_ok=True)
+            prdc.save_rows('%s/epoch%d-%s-prdc.npz' % (d, epoch, tag), acc.rows(), res, acc.k)
+        out['prdc_clips_nonfinite'] = res['clips_nonfinite']
+        return out
 
 
 class ClipMetrics(ClipTable):

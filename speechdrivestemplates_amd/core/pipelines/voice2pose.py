@@ -297,7 +297,9 @@ class Voice2Pose(Trainer):
         super().__init__(cfg)
         self.fgd_observer, self.clip_observer, self.sync_observer, self.motion_observer = (
             vo.DeviceFGD(self), vo.ClipMetrics(self), vo.SyncMetrics(self), vo.MotionDist(self))
-        self._val_observers = [self.fgd_observer, self.clip_observer, vo.FitClipMetrics(self), self.sync_observer, self.motion_observer]
+        self.prdc_observer = vo.FeatureSets(self)
+        self._val_observers = [self.fgd_observer, self.prdc_observer, self.clip_observer, vo.FitClipMetrics(self), self.sync_observer,
+                               self.motion_observer]
 
     def setup_model(self, cfg, state_dict=None, external_codes=None):
         # kernel routing this pipeline's configuration asks for -- set UNCONDITIONALLY (defaults included: a pipeline built after a bf16 one in the
@@ -586,9 +588,12 @@ class Voice2Pose(Trainer):
         return {'L2_dist': l2.mean(), 'lip_sync_error_n': torch.abs(lp / den - lg / den).mean()}
 
     def val_observers(self):
-        """device FGD, clip metrics, fitted-clip metrics, synchrony, motion histograms: this order is the key order of validate()'s result.
-        The four lookups below give an observer's accumulator (None before the first validation step with its key on)."""
+        """device FGD, feature-set metrics, clip metrics, fitted-clip metrics, synchrony, motion histograms: this order is the key order of
+        validate()'s result.  The lookups below give an observer's accumulator (None before the first validation step with its key on)."""
         return self._val_observers
+
+    def feature_sets(self):
+        return self.prdc_observer.acc
 
     def device_fgd(self):
         return self.fgd_observer.acc
