@@ -1229,6 +1229,41 @@ int sdt_prdc_cross(const double* q, const int64_t* qcount, int64_t qcap, const d
 int sdt_prdc_reduce(const int64_t* counts, int64_t real_cap, int64_t gen_cap, int k, const double* r_real, const int64_t* gen_balls,
                     const int64_t* real_balls, const double* real_nearest_d2, int64_t* covered, int64_t* recalled, int64_t* out, void* stream);
 
+/*
+ * Bootstrap over the clips of a record table (TEST.BOOTSTRAP; speechdrivestemplates_amd/bootstrap.py; DESIGN.md section 34 is the contract,
+ * bootstrap.stages_model is the same operations in numpy).  Float words are float64 carried in 8-byte words, every operation rounded on its
+ * own (csrc/exact_f64.h); integer words are added exactly; no floating-point atomics.  No allocation; every pointer except ``tables_a``,
+ * ``tables_b`` and ``part_sizes`` (host arrays, read during the call) is a device buffer; every size is checked before the launch.
+ *   sdt_clip_metrics_replicate_dense: the live clips of the clip-metrics tables (sdt_clip_metrics_epoch's ``tables``: per clip the record of
+ *     the lowest rank with seen set; live = there is one and its nonfinite word is 0 -- with ranks_b > 0 in BOTH sets), in clip order, as
+ *     dense rows of 39 words: the record's words [0, 36) (20 float sums, 16 hit counts), then copies * frames, copies * (frames - 1),
+ *     copies * (copies - 1) / 2 * frames.  dense_a (dense_b): N x 39 words, the first n filled; n_out[0] = n.  point_a (point_b): 39 words,
+ *     the sums of the set's live rows in the order of the epoch stage: chunks of 64 clips OF THE TABLE in index order, then the chunk
+ *     partials in order (with one set these are the totals sdt_clip_metrics_epoch divides).  work: ceil(N / 64) * 80 words.  With
+ *     ranks_b == 0 the three pointers of the second set are NULL.
+ *   sdt_bootstrap_sums: generic.  dense: n rows of ``words`` (1 .. 64) words, the first ``float_words`` float64, the rest int64.  Draw i
+ *     (0 .. n - 1) of replicate r (0 .. replicates - 1) is row (uint64(w) * n) >> 32, w = word i & 3 of Philox4x32-10 with the counter
+ *     (i >> 2, 3, r, 0) and the key (seed low word, seed high word).  sums[r] (``words`` words) adds the n drawn rows in chunks of 64 draws
+ *     in draw order, then the chunk partials in order.  work: replicates * ceil(n / 64) * words words.  n < 2^31, replicates <= 65535.
+ *   sdt_clip_metrics_replicate_values: the final divisions of sdt_clip_metrics_epoch on each of ``rows`` sum rows of 39 words: values
+ *     (rows x 36 float64, the words [0, 36) of the epoch vector) and pair_frames (rows int64, the (pair, frame) terms behind diversity).
+ *   sdt_bootstrap_diff_f64: d[i] = a[i] - b[i].
+ *   sdt_bootstrap_intervals_f64: values is (replicates, cols) float64; lohi (cols x 2) takes per column the order statistics at ranks
+ *     ``rank`` and replicates - 1 - rank (0 <= 2 rank < replicates) in the order of csrc/radix_select.h's order_key, by eight digit passes:
+ *     each is one of the inputs.  counts: NULL, or cols x 3 int64 = per column the number of values < 0, > 0, == 0.
+ */
+#define SDT_BOOTSTRAP_CLIP_WORDS 39
+#define SDT_BOOTSTRAP_CLIP_VALUES 36
+#define SDT_BOOTSTRAP_DENSE_WORK 80
+int sdt_clip_metrics_replicate_dense(const void* const* tables_a, int ranks_a, const void* const* tables_b, int ranks_b, int64_t N, void* work,
+                                     void* dense_a, void* dense_b, void* point_a, void* point_b, int64_t* n_out, void* stream);
+int sdt_bootstrap_sums(const void* dense, int64_t n, int words, int float_words, int replicates, uint64_t seed, void* work, void* sums,
+                       void* stream);
+int sdt_clip_metrics_replicate_values(const void* sums, int64_t rows, const int64_t* part_sizes, int num_alphas, void* values,
+                                      void* pair_frames, void* stream);
+int sdt_bootstrap_diff_f64(const double* a, const double* b, int64_t n, double* d, void* stream);
+int sdt_bootstrap_intervals_f64(const double* values, int64_t replicates, int cols, int64_t rank, double* lohi, int64_t* counts, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

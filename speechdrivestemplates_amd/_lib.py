@@ -229,6 +229,11 @@ SIGNATURES = {
     "sdt_prdc_knn": [_p, _p, _i64, _i, _i, _i, _p, _i64, _p, _p],
     "sdt_prdc_cross": [_p, _p, _i64, _p, _p, _i64, _p, _i, _i, _p, _i64, _p, _p, _p, _p],
     "sdt_prdc_reduce": [_p, _i64, _i64, _i, _p, _p, _p, _p, _p, _p, _p, _p],
+    "sdt_clip_metrics_replicate_dense": [C.POINTER(C.c_void_p), _i, C.POINTER(C.c_void_p), _i, _i64, _p, _p, _p, _p, _p, _p, _p],
+    "sdt_bootstrap_sums": [_p, _i64, _i, _i, _i, C.c_uint64, _p, _p, _p],
+    "sdt_clip_metrics_replicate_values": [_p, _i64, C.POINTER(C.c_int64), _i, _p, _p, _p],
+    "sdt_bootstrap_diff_f64": [_p, _p, _i64, _p, _p],
+    "sdt_bootstrap_intervals_f64": [_p, _i64, _i, _i64, _p, _p, _p],
 }
 F32, BF16 = 0, 1  # enum sdt_dtype
 

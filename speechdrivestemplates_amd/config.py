@@ -146,7 +146,20 @@ _DEFAULTS = {
              # was, nothing constructed or launched.  K: neighbours of a radius, an integer 1 .. 16; 5 is the value of the density /
              # coverage paper and UNTUNED for validation sets of a few hundred clips.  Not verified: real data, a trained encoder, a
              # multi-GPU run.
-             "PRDC": {"ENABLE": False, "K": 5}},
+             "PRDC": {"ENABLE": False, "K": 5},
+             # extension (bootstrap intervals of the clip metrics, bootstrap.clip_metric_intervals / csrc/bootstrap.hip; DESIGN.md section
+             # 34; needs CLIP_METRICS).  ENABLE True = validate() / test() resample the clips of the gathered clip-metrics table with
+             # replacement REPLICATES times on the GPU (no second all-gather, the same bits on every rank) and add, for every metric key of
+             # TEST.CLIP_METRICS, <key>_lo and <key>_hi: the percentile interval of coverage LEVEL, the order statistics at ranks
+             # floor(REPLICATES (1 - LEVEL) / 2) from either end of the replicate values.  With FIT_CODE the _fit keys get <key>_fit_lo /
+             # _hi too, and one paired run of the fitted against the plain prediction (the same draws for both) adds <key>_fit_gain_lo /
+             # _hi, the interval of fitted minus plain, for L2_hands, PCK and PCK_hands.  With SAVE_NPZ the master also writes
+             # results/epoch<E>-<TAG>-clip_bootstrap.npz (the replicate values, their names, the point row, n, R, level, seed, part
+             # sizes).  The intervals are percentile intervals without bias correction, and they take the clips as independent: clips cut
+             # from one recording are not, so on such sets they are optimistic.  FGD, PRDC, synchrony and motion-distance values are not
+             # covered.  REPLICATES: an integer 100 .. 20000.  LEVEL in (0, 1).  SEED in [0, 2^64): the Philox key of the draws.  False =
+             # the loop as it was, nothing constructed or launched.
+             "BOOTSTRAP": {"ENABLE": False, "REPLICATES": 1000, "LEVEL": 0.95, "SEED": 0}},
     "DEMO": {"MULTIPLE": 1, "NUM_SAMPLES": 1, "CODE_INDEX": None, "CODE_INDEX_B": None, "CODE_PATH": None,
              # extensions (the whole-recording demo, long_demo.LongDemo / csrc/long_demo.hip; Voice2Pose only).
              # LONG_FORM True = a demo input of F >= DATASET.NUM_FRAMES frames is generated as overlapping windows of NUM_FRAMES frames (the
@@ -459,6 +472,31 @@ def check_prdc(cfg):
     if cfg.VOICE2POSE.POSE_ENCODER.NAME is None:
         raise ValueError("TEST.PRDC.ENABLE needs VOICE2POSE.POSE_ENCODER.NAME (the features are the pose encoder's mu and logvar), got None")
     return {'k': int(k)}
+
+
+def check_bootstrap(cfg):
+    """Validate TEST.BOOTSTRAP (ValueError names the key; the ranges are checked whether or not the key is on).  Returns None with ENABLE
+    off, else {'replicates', 'level', 'seed', 'rank'} as Python values (rank = floor(REPLICATES (1 - LEVEL) / 2))."""
+    from .bootstrap import MAX_REPLICATES, MIN_REPLICATES, rank_of
+    b, pre = cfg.TEST.BOOTSTRAP, "TEST.BOOTSTRAP."
+    on, reps, level, seed = b.ENABLE, b.REPLICATES, b.LEVEL, b.SEED
+    if not isinstance(on, bool):
+        raise ValueError(pre + "ENABLE must be True or False, got %r" % (on,))
+    if not _is_int(reps) or not MIN_REPLICATES <= reps <= MAX_REPLICATES:
+        raise ValueError(pre + "REPLICATES must be an integer from %d to %d, got %r" % (MIN_REPLICATES, MAX_REPLICATES, reps))
+    if not _is_number(level) or not 0 < level < 1:
+        raise ValueError(pre + "LEVEL must be a number in (0, 1), got %r" % (level,))
+    rank = rank_of(reps, level)
+    if not 2 * rank < reps:
+        raise ValueError(pre + "LEVEL %r puts the rank %d outside [0, REPLICATES / 2)" % (level, rank))
+    if not _is_int(seed) or not 0 <= seed < 1 << 64:
+        raise ValueError(pre + "SEED must be an integer in [0, 2^64), got %r" % (seed,))
+    if not on:
+        return None
+    if cfg.TEST.CLIP_METRICS is not True:
+        raise ValueError(pre + "ENABLE needs TEST.CLIP_METRICS (the intervals are those of the clip-metrics table), got %r"
+                         % (cfg.TEST.CLIP_METRICS,))
+    return {'replicates': int(reps), 'level': float(level), 'seed': int(seed), 'rank': rank}
 
 
 def check_augment(cfg):

@@ -41,14 +41,15 @@ class Trainer(object):
         if not torch.cuda.is_available():
             raise RuntimeError('this engine needs an AMD GPU (no CPU fallback); torch.cuda.is_available() is False')
         torch.cuda.set_device(int(os.environ.get('LOCAL_RANK', self.get_rank() % max(1, torch.cuda.device_count()))))
-        from ...config import (check_augment, check_clip_metrics, check_fit_code, check_histograms, check_long_demo, check_motion_dist,
-                               check_prdc, check_sync_metrics)
+        from ...config import (check_augment, check_bootstrap, check_clip_metrics, check_fit_code, check_histograms, check_long_demo,
+                               check_motion_dist, check_prdc, check_sync_metrics)
         check_histograms(cfg)  # SYS.HISTOGRAM_INTERVAL without SYS.TENSORBOARD: there is nowhere to write
         check_clip_metrics(cfg)  # TEST.CLIP_METRICS / TEST.PCK_ALPHAS (a Voice2Pose key)
         check_sync_metrics(cfg)  # TEST.SYNC_METRICS / SYNC_TOLERANCE / SYNC_SIGMA (a Voice2Pose key)
         check_motion_dist(cfg)  # TEST.MOTION_DIST / MOTION_DIST_EDGES (a Voice2Pose key)
         check_fit_code(cfg)  # TEST.FIT_CODE: oracle-code validation (a Voice2Pose key)
         check_prdc(cfg)  # TEST.PRDC: precision / recall / density / coverage of the generated feature set (a Voice2Pose key)
+        check_bootstrap(cfg)  # TEST.BOOTSTRAP: percentile intervals of the clip metrics (needs TEST.CLIP_METRICS)
         check_long_demo(cfg)  # DEMO.LONG_FORM and its window / smoothing / segment keys (a Voice2Pose key)
         check_augment(cfg)  # TRAIN.AUGMENT: audio augmentation inside the train step (a Voice2Pose key)
 

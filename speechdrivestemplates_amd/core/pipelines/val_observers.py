@@ -94,7 +94,13 @@ class ClipTable(_Observer):
             tables = [acc.table()] if gathered is None else [g[:acc.num_clips] for g in gathered]
             module.save_table('%s/epoch%d-%s-%s_metrics.npz' % (d, epoch, tag, self.label), module.merge_tables([t.cpu().numpy() for t in tables]),
                               *self.save_args())
-        return {k + self.suffix: v for k, v in res.items() if k not in module.BOOKKEEPING}
+        out = {k + self.suffix: v for k, v in res.items() if k not in module.BOOKKEEPING}
+        out.update(self.intervals(res, gathered, epoch, tag))
+        return out
+
+    def intervals(self, res, gathered, epoch, tag):
+        """what a family adds from the gathered states it already has, after its own keys (nothing, unless it says otherwise)"""
+        return {}
 
 
 class FeatureSets(ClipTable):
@@ -149,6 +155,33 @@ class ClipMetrics(ClipTable):
     def save_args(self):
         return (self.acc.alphas,)
 
+    def reset(self):
+        ClipTable.reset(self)
+        self.resampled = None  # after an epoch with TEST.BOOTSTRAP: (the gathered states,), for the paired run of FitClipMetrics
+
+    def intervals(self, res, gathered, epoch, tag):
+        """TEST.BOOTSTRAP: <key>_lo / <key>_hi for every metric key of ``res``, from the states the epoch has gathered (bootstrap.py)"""
+        from ...config import check_bootstrap
+        opts, pipe = check_bootstrap(self.pipe.cfg), self.pipe
+        if opts is None:
+            return {}
+        from ... import bootstrap
+        self.resampled = (gathered,)
+        run = dict(replicates=opts['replicates'], level=opts['level'], seed=opts['seed'])
+        stages = {}
+        ci = bootstrap.clip_metric_intervals(self.acc, gathered=gathered, stages=stages, **run)
+        if not ci:
+            logging.warning('[VAL] %s metrics: no live clip, no bootstrap intervals' % self.label)
+            return {}
+        if pipe.is_master_process() and pipe.cfg.TEST.SAVE_NPZ and pipe.base_path is not None:
+            bootstrap.save_replicates('%s/results/epoch%d-%s-%s_bootstrap.npz' % (pipe.base_path, epoch, tag, self.label), stages,
+                                      self.acc.alphas, clip_metrics.part_sizes(self.acc.parts), **run)
+        out = {}
+        for k in res:
+            if k in ci:
+                out[k + self.suffix + '_lo'], out[k + self.suffix + '_hi'] = ci[k][1], ci[k][2]
+        return out
+
 
 class FitClipMetrics(ClipMetrics):
     """with TEST.FIT_CODE: a second table for the fitted predictions ``fit_code_step`` left in ``ctx.fit_p``, one copy per clip; keys end in _fit"""
@@ -159,6 +192,23 @@ class FitClipMetrics(ClipMetrics):
 
     def step(self, ctx):
         ClipMetrics.step(self, SimpleNamespace(batch=ctx.batch, fin_p=ctx.fit_p, fin_g=ctx.fin_g, multiple=1))
+
+    def intervals(self, res, gathered, epoch, tag):
+        """the _fit keys' own intervals, then one paired run of the fitted against the plain prediction over the clips live in both tables:
+        <key>_fit_gain_lo / _hi, the interval of fitted minus plain"""
+        out = ClipMetrics.intervals(self, res, gathered, epoch, tag)
+        plain = getattr(self.pipe, 'clip_observer', None)
+        if not out or plain is None or plain.acc is None or getattr(plain, 'resampled', None) is None:
+            return out
+        from ... import bootstrap
+        from ...config import check_bootstrap
+        opts = check_bootstrap(self.pipe.cfg)
+        gain = bootstrap.clip_metric_paired(self.acc, plain.acc, replicates=opts['replicates'], level=opts['level'], seed=opts['seed'],
+                                            gathered_a=gathered, gathered_b=plain.resampled[0])
+        for k in bootstrap.GAIN_KEYS:
+            if k in gain:
+                out[k + '_fit_gain_lo'], out[k + '_fit_gain_hi'] = gain[k]['diff_lo'], gain[k]['diff_hi']
+        return out
 
 
 class SyncMetrics(ClipTable):
