@@ -1264,6 +1264,51 @@ int sdt_clip_metrics_replicate_values(const void* sums, int64_t rows, const int6
 int sdt_bootstrap_diff_f64(const double* a, const double* b, int64_t n, double* d, void* stream);
 int sdt_bootstrap_intervals_f64(const double* values, int64_t replicates, int cols, int64_t rank, double* lohi, int64_t* counts, void* stream);
 
+/*
+ * The audio band under the rendered pictures (SYS.AUDIO_STRIP; speechdrivestemplates_amd/audio_strip.py; DESIGN.md section 35 is the contract,
+ * audio_strip.envelope_model / raster_model / compose_model are the same operations in numpy).  Every decision is integer arithmetic, a
+ * comparison or one IEEE operation rounded on its own; minima and maxima are taken on an integer order key (-0 below +0); a non-finite sample is
+ * selected away, never compared; the only atomics are integer ones.  No allocation; every pointer except ``colours``, ``background`` and
+ * ``playhead`` (host arrays of BGR bytes, read during the call) is a device buffer; every size is checked before the launch.
+ *   sdt_strip_envelope_f32: audio (L,) float32; bounds (Nc + 1,) int64 ascending, the columns' start samples.  Column c covers the samples
+ *     [max(bounds[c], 0), min(bounds[c + 1], L)): env[2 c], env[2 c + 1] = the min and max of its finite samples (0 without one), flags[c] =
+ *     SDT_STRIP_EMPTY (no sample), SDT_STRIP_NONFINITE (a NaN or an infinity among them) or SDT_STRIP_OK.  stats[0] = the bits of max |x| over
+ *     the finite samples of the whole recording (a float32 in the low word, 0 without one), stats[1] = the number of non-finite samples.
+ *   sdt_strip_raster_u8: the band (S, Nc, 3) uint8 BGR from the envelope, the power mel (n_mels, F) float32, colormap (256, 3) uint8 BGR,
+ *     factors (255,) float32 ascending and three lists of int32 ticks of 1/300 s (n = 0: an absent list).  From the top: a waveform lane of
+ *     Sw = 3 S / 8 rows, SDT_STRIP_MARK_LANES mark lanes of SDT_STRIP_MARK_ROWS rows, a mel lane of Sm rows (the rest).
+ *     Waveform: sample x sits in row clamp(floor((1 - x g) (Sw - 1) / 2 + 0.5), 0, Sw - 1), g = 1 / max(peak, 2^-15), float64, each operation
+ *     rounded on its own; an OK column has colours[1] from the row of its max to the row of its min, colours[0] elsewhere; a NONFINITE column
+ *     is colours[2] over the lane; an EMPTY one colours[0].  Marks: tick k >= 0 is at sample k * 16000 / 300 and colours, in lane q,
+ *     colours[3 + q] in the column that holds that sample and the SDT_STRIP_TICK_WIDTH - 1 columns after it; ticks outside
+ *     [bounds[0], bounds[Nc]) are ignored.  Mel: pixel (y, c) takes frame min(max((bounds[c] + bounds[c + 1]) >> 1, 0) / 160, F - 1) and bin
+ *     n_mels (Sm - 1 - y) / Sm; its colour is colormap[the number of i with p >= fl32(ref * factors[i])], ref = the largest finite power of
+ *     the mel, at least +0 (work[0], never read back); a non-finite power is colours[2]; an EMPTY column is colours[0].  work: 8 bytes.
+ *   sdt_strip_compose_u8: out (n, H + S, W, 3): rows [0, H) of image i are those of frames (n, H, W, 3); row H + y is row y of the band,
+ *     columns [c0[i], c0[i] + W), ``background`` where that leaves [0, Nc); ``playhead`` over columns [ph[i] - c0[i], + SDT_STRIP_PLAYHEAD_WIDTH)
+ *     unless ph[i] < 0.  16 bytes per lane when W * 3 and both base addresses are multiples of 16 (sdt_strip_compose_vectorised returns 1),
+ *     else a byte per lane.
+ */
+#define SDT_STRIP_EMPTY 0
+#define SDT_STRIP_NONFINITE 1
+#define SDT_STRIP_OK 2
+#define SDT_STRIP_MARK_LANES 3
+#define SDT_STRIP_MARK_ROWS 8
+#define SDT_STRIP_TICK_WIDTH 2
+#define SDT_STRIP_PLAYHEAD_WIDTH 2
+#define SDT_STRIP_COLOURS 6
+#define SDT_STRIP_MIN_HEIGHT 64
+#define SDT_STRIP_MAX_HEIGHT 1024
+#define SDT_STRIP_MAX_COLUMNS (1 << 24)
+int sdt_strip_envelope_f32(const float* audio, int64_t L, const int64_t* bounds, int Nc, float* env, int32_t* flags, int64_t* stats,
+                           void* stream);
+int sdt_strip_raster_u8(const float* env, const int32_t* flags, const int64_t* stats, const int64_t* bounds, int Nc, const float* mel, int n_mels,
+                        int64_t F, const uint8_t* colormap, const float* factors, const int32_t* ticks0, int n0, const int32_t* ticks1, int n1,
+                        const int32_t* ticks2, int n2, const uint8_t* colours, int S, void* work, uint8_t* band, void* stream);
+int sdt_strip_compose_u8(const uint8_t* frames, int64_t n, int H, int W, const uint8_t* band, int S, int Nc, const int32_t* c0, const int32_t* ph,
+                         const uint8_t* background, const uint8_t* playhead, uint8_t* out, int64_t out_bytes, void* stream);
+int sdt_strip_compose_vectorised(const void* frames, int W, const void* out);
+
 #ifdef __cplusplus
 }
 #endif

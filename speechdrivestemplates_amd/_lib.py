@@ -234,6 +234,10 @@ SIGNATURES = {
     "sdt_clip_metrics_replicate_values": [_p, _i64, C.POINTER(C.c_int64), _i, _p, _p, _p],
     "sdt_bootstrap_diff_f64": [_p, _p, _i64, _p, _p],
     "sdt_bootstrap_intervals_f64": [_p, _i64, _i, _i64, _p, _p, _p],
+    "sdt_strip_envelope_f32": [_p, _i64, _p, _i, _p, _p, _p, _p],
+    "sdt_strip_raster_u8": [_p, _p, _p, _p, _i, _p, _i, _i64, _p, _p, _p, _i, _p, _i, _p, _i, _p, _i, _p, _p, _p],
+    "sdt_strip_compose_u8": [_p, _i64, _i, _i, _p, _i, _i, _p, _p, _p, _p, _p, _i64, _p],
+    "sdt_strip_compose_vectorised": [_p, _i, _p],  # (returns 0 / 1)
 }
 F32, BF16 = 0, 1  # enum sdt_dtype
 

@@ -218,7 +218,15 @@ _DEFAULTS = {
             "DDP_UNSYNCED_D": False,
             # EVAL_WITH_EMA True = validate(), test() and demo() run on the EMA weights (TRAIN.EMA_DECAY, or a checkpoint that carries
             # 'model_ema_state_dict'); the training weights are back, bit for bit, when they return.  False = the training weights.
-            "EVAL_WITH_EMA": False},
+            "EVAL_WITH_EMA": False,
+            # AUDIO_STRIP (the audio under the gestures, audio_strip.py / csrc/audio_strip.hip; Voice2Pose only; needs
+            # RENDER_VIDEO, DATASET.AUDIO_SR 16000 and DATASET.FPS 15).  ENABLE True = every pair video, demo video and long image gets a band
+            # of HEIGHT rows (a multiple of 16 from 64 to 512) appended below the canvas, drawn on the GPU: the waveform envelope, with MARKS
+            # the audio onsets and the motion beats of part 'all' that sync_metrics detects (prediction, and ground truth in pair videos),
+            # the mel spectrogram of the clean audio over DB_RANGE dB (20 .. 120) below its largest power and, in videos, a playhead.  A clip
+            # of at most SPAN_S seconds (1 .. 60) shows its whole audio; a longer one scrolls with the playhead in the middle.  The skeleton
+            # rows of every picture keep their bytes.  False = nothing is imported, constructed or launched; every file as it was.
+            "AUDIO_STRIP": {"ENABLE": False, "HEIGHT": 160, "SPAN_S": 4.3, "MARKS": True, "DB_RANGE": 80.0}},
 }
 
 
@@ -622,6 +630,39 @@ def check_long_demo(cfg):
     if cfg.VOICE2POSE.GENERATOR.CLIP_CODE.TEST_WITH_GT_CODE:
         raise ValueError("DEMO.LONG_FORM cannot run with VOICE2POSE.GENERATOR.CLIP_CODE.TEST_WITH_GT_CODE: a demo input has no ground truth")
     return {'overlap': O, 'batch': batch, 'smooth': None if smooth is None else (smooth[0], smooth[1]), 'segment': seg}
+
+
+def check_audio_strip(cfg):
+    """Validate SYS.AUDIO_STRIP (ValueError names the key; the numbers are checked whether or not the key is on).  Returns None with the key
+    off, else {'height', 'span_s', 'marks', 'db_range'}."""
+    a, pre = cfg.SYS.AUDIO_STRIP, "SYS.AUDIO_STRIP."
+    on, height, span, marks, db = a.ENABLE, a.HEIGHT, a.SPAN_S, a.MARKS, a.DB_RANGE
+    if not isinstance(on, bool):
+        raise ValueError(pre + "ENABLE must be True or False, got %r" % (on,))
+    if not isinstance(marks, bool):
+        raise ValueError(pre + "MARKS must be True or False, got %r" % (marks,))
+    if not _is_int(height) or height % 16 or not 64 <= height <= 512:
+        raise ValueError(pre + "HEIGHT must be a multiple of 16 from 64 to 512 (rows of the band), got %r" % (height,))
+    if not _is_number(span) or not 1 <= span <= 60:
+        raise ValueError(pre + "SPAN_S must be a number of seconds from 1 to 60, got %r" % (span,))
+    if not _is_number(db) or not 20 <= db <= 120:
+        raise ValueError(pre + "DB_RANGE must be a number of decibels from 20 to 120, got %r" % (db,))
+    if not on:
+        return None
+    if not cfg.SYS.RENDER_VIDEO:
+        raise ValueError(pre + "ENABLE needs SYS.RENDER_VIDEO: the band goes under the rendered pictures")
+    if cfg.PIPELINE_TYPE != "Voice2Pose":
+        raise ValueError(pre + "ENABLE is a Voice2Pose key (Pose2Pose has no audio), got PIPELINE_TYPE %r" % (cfg.PIPELINE_TYPE,))
+    if cfg.DATASET.AUDIO_SR != 16000:
+        raise ValueError(pre + "ENABLE needs DATASET.AUDIO_SR 16000 (a mel hop is 160 samples, a tick 160 / 3), got %r" % (cfg.DATASET.AUDIO_SR,))
+    if cfg.DATASET.FPS != 15:
+        raise ValueError(pre + "ENABLE needs DATASET.FPS 15 (a pose frame is 20 ticks of 1/300 s), got %r" % (cfg.DATASET.FPS,))
+    if cfg.SYS.DEVICE_JPEG or "avi" in cfg.SYS.VIDEO_FORMAT:  # the GPU encoder takes pictures of at most 65535 rows and columns (jpeg.py)
+        H, W = (int(v) for v in cfg.SYS.CANVAS_SIZE)
+        if max(H + height, W) > 65535:
+            raise ValueError(pre + "HEIGHT: the GPU JPEG encoder (SYS.DEVICE_JPEG, 'avi') takes at most 65535 rows and columns, got "
+                             "%d + %d rows of %d" % (H, height, W))
+    return {'height': int(height), 'span_s': float(span), 'marks': marks, 'db_range': float(db)}
 
 
 def check_histograms(cfg):

@@ -41,8 +41,8 @@ class Trainer(object):
         if not torch.cuda.is_available():
             raise RuntimeError('this engine needs an AMD GPU (no CPU fallback); torch.cuda.is_available() is False')
         torch.cuda.set_device(int(os.environ.get('LOCAL_RANK', self.get_rank() % max(1, torch.cuda.device_count()))))
-        from ...config import (check_augment, check_bootstrap, check_clip_metrics, check_fit_code, check_histograms, check_long_demo,
-                               check_motion_dist, check_prdc, check_sync_metrics)
+        from ...config import (check_audio_strip, check_augment, check_bootstrap, check_clip_metrics, check_fit_code, check_histograms,
+                               check_long_demo, check_motion_dist, check_prdc, check_sync_metrics)
         check_histograms(cfg)  # SYS.HISTOGRAM_INTERVAL without SYS.TENSORBOARD: there is nowhere to write
         check_clip_metrics(cfg)  # TEST.CLIP_METRICS / TEST.PCK_ALPHAS (a Voice2Pose key)
         check_sync_metrics(cfg)  # TEST.SYNC_METRICS / SYNC_TOLERANCE / SYNC_SIGMA (a Voice2Pose key)
@@ -52,6 +52,7 @@ class Trainer(object):
         check_bootstrap(cfg)  # TEST.BOOTSTRAP: percentile intervals of the clip metrics (needs TEST.CLIP_METRICS)
         check_long_demo(cfg)  # DEMO.LONG_FORM and its window / smoothing / segment keys (a Voice2Pose key)
         check_augment(cfg)  # TRAIN.AUGMENT: audio augmentation inside the train step (a Voice2Pose key)
+        self.strip_opts = check_audio_strip(cfg)  # SYS.AUDIO_STRIP: the audio band under the rendered pictures (None = off)
 
     # -- process-group helpers (trainer.py:29-45) ---------------------------------------------------------
     def get_rank(self):
@@ -323,6 +324,8 @@ class Trainer(object):
     def write_pair_video(self, tag, pred, gt, t_step, epoch, global_step=None, audio=None):
         """clip 0's prediction beside its ground truth, with clip 0's audio (final poses, (T, 2, K))"""
         vid_batch = self.generate_video_pair(pred, gt)
+        if self.strip_opts is not None and audio is not None:  # SYS.AUDIO_STRIP
+            vid_batch, _ = self.add_audio_strip(vid_batch, None, audio[0], pred, gt)
         self.setup_video_writer().save_video(self.cfg, tag, vid_batch, t_step, epoch, global_step,
                                              audio=None if audio is None else audio[0], writer=getattr(self, 'tb_writer', None),
                                              base_path=self.base_path)
@@ -331,8 +334,24 @@ class Trainer(object):
         from ... import render
         vid_batch = self.generate_video(pred)
         long_img = render.render_long_image(pred)
+        if self.strip_opts is not None and audio is not None:  # SYS.AUDIO_STRIP
+            vid_batch, long_img = self.add_audio_strip(vid_batch, long_img, audio[0], pred, None)
         self.setup_video_writer().save_video(self.cfg, 'DEMO', vid_batch, t_step, epoch, long_img=long_img,
                                              audio=None if audio is None else audio[0], base_path=self.base_path, extra_id=extra_id)
+
+    def add_audio_strip(self, frames, long_img, audio, pred, gt):
+        """SYS.AUDIO_STRIP: the band of one clip's audio under its frames and (demo) its long image (audio_strip.py).
+        ``audio`` (L,) as the loader delivered it: the mel is the model's own front end on that clean audio; with MARKS the onsets and the
+        beats of part 'all' come from sync_metrics, unchanged.  -> (frames, long image or None)"""
+        from ... import audio_strip
+        o = self.strip_opts
+        x = audio.detach().to(device=frames.device, dtype=torch.float32).contiguous()
+        mel = self.model.mel_transfm(x[None])[0]
+        marks = audio_strip.clip_marks(x, pred, gt) if o['marks'] else None
+        out = audio_strip.strip_for_clip(frames, x, mel, marks, o['height'], o['span_s'], o['db_range'])
+        if long_img is not None:
+            long_img = audio_strip.strip_for_long_image(long_img, x, mel, int(pred.shape[0]), marks, o['height'], o['db_range'])
+        return out, long_img
 
     # -- epoch figures (trainer.py:227-231,404-405; voice2pose.py:479-510; pose2pose.py:314-345) --------------------------------
     def draw_figure_epoch(self):
