@@ -79,7 +79,7 @@ def test_conv2d(ops, case):
 
 @pytest.mark.parametrize("mode,tol", [("f32", 3e-6), ("bf16x6", 3e-6), ("bf16x3", 1e-4), ("bf16", 1.5e-2)])
 def test_conv_math_modes(ops, mode, tol):
-    """Opt-in product arithmetic of the forward / input-gradient kernels (sdt_set_conv_math): fp32 in and out in every
+    """Opt-in product arithmetic of the forward / input-gradient / weight-gradient kernels (sdt_set_conv_math): fp32 in and out in every
     mode; 'bf16x6' (exact 3-piece split of both operands, 6 bf16 MFMA products) must be as accurate as the exact-fp32
     MFMA kernel; 'bf16' is BASELINE config 4's precision.  Error is max|d| / max|ref| against float64."""
     g = torch.Generator().manual_seed(77)
@@ -90,16 +90,19 @@ def test_conv_math_modes(ops, mode, tol):
         for B, Hi, Wi, Cin, Cout, kh, kw, s, p in cases:
             x = torch.randn(B, Cin, Hi, Wi, generator=g, dtype=torch.float64)
             w = torch.randn(Cout, Cin, kh, kw, generator=g, dtype=torch.float64) * (2.0 / (Cin * kh * kw)) ** 0.5
-            xr = x.clone().requires_grad_(True)
-            y = F.conv2d(xr, w, None, s, p)
+            xr, wr = x.clone().requires_grad_(True), w.clone().requires_grad_(True)
+            y = F.conv2d(xr, wr, None, s, p)
             gy = torch.randn(y.shape, generator=g, dtype=torch.float64)
             y.backward(gy)
             wd = torch.nn.Parameter(ops.to_weight_layout(w.float()).to(DEV))
             xd = ops.cl(x.float()).to(DEV)
+            gyd = ops.cl(gy.float()).to(DEV)
             yd = ops.conv_forward(xd, wd, None, s, p)
-            dxd = ops.conv_input_grad(ops.cl(gy.float()).to(DEV), wd, xd.shape, s, p)
+            dxd = ops.conv_input_grad(gyd, wd, xd.shape, s, p)
+            ops.conv_weight_grad(xd, gyd, wd, s, p)
             check("%s fwd" % mode, ops.cf_view(yd), y, tol)
             check("%s dX" % mode, ops.cf_view(dxd), xr.grad, tol)
+            check("%s dW" % mode, wd.grad, wr.grad, tol)  # (conv_dw_kernel<.., true, NS> under a mode: fp32 atomics)
     finally:
         ops.set_conv_math("f32")
     with pytest.raises(KeyError):
