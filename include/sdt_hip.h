@@ -22,6 +22,8 @@ extern "C" {
 #endif
 
 #define SDT_MAX_TAPS 20
+/* What sdt_abi_version() of a library built from this header returns: a consumer compares the two to catch a stale .so */
+#define SDT_ABI_VERSION 5
 
 enum sdt_status { SDT_OK = 0, SDT_ERR_ARG = -1, SDT_ERR_LAUNCH = -2, SDT_ERR_UNSUPPORTED = -3 };
 /* Element type of a tensor argument of the *_t / *_bf16 entry points (the bf16-storage path of BASELINE config 4: activations of the

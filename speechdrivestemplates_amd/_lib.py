@@ -271,6 +271,7 @@ def load():
             "libsdt_hip.so not found at %s -- run `python __graft_entry__.py` (hipcc --offload-arch=gfx950) first; "
             "this package has no CPU fallback" % LIB_PATH)
     lib = C.CDLL(LIB_PATH)
+    lib.sdt_abi_version.argtypes = []
     lib.sdt_abi_version.restype = C.c_int
     if lib.sdt_abi_version() != ABI_VERSION:  # checked BEFORE binding: a stale .so fails here, not with an AttributeError on a new symbol
         raise ImportError("libsdt_hip.so at %s has ABI version %d, this package needs %d -- rebuild it (python __graft_entry__.py)"
@@ -326,7 +327,9 @@ def load():
     lib.sdt_convsk_dw_workspace_bytes.restype = C.c_int64
     lib.sdt_convsk_workspace_bytes.argtypes = []
     lib.sdt_convsk_workspace_bytes.restype = C.c_int64
+    lib.sdt_last_error.argtypes = []
     lib.sdt_last_error.restype = C.c_char_p
+    lib.sdt_get_conv_math.argtypes = []
     lib.sdt_get_conv_math.restype = C.c_int
     _lib = lib
     return lib

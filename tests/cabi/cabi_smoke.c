@@ -3,13 +3,46 @@
 #include <stdio.h>
 #include <string.h>
 
+#include <stddef.h>
+
 #include "sdt_hip.h"
+
+/* The structures' layout as the header's fields intend it, checked where a C consumer compiles (C11: _Static_assert; C99: an array
+ * type of negative size).  The counts are the header's field lists: tests/test_abi_contract_host.py holds the ctypes mirrors of
+ * speechdrivestemplates_amd/_lib.py to the same numbers through the compiler. */
+#if defined(__STDC_VERSION__) && __STDC_VERSION__ >= 201112L
+#define SDT_STATIC_ASSERT(cond, name) _Static_assert(cond, #name)
+#else
+#define SDT_STATIC_ASSERT(cond, name) typedef char sdt_static_assert_##name[(cond) ? 1 : -1]
+#endif
+SDT_STATIC_ASSERT(SDT_ABI_VERSION == 5, abi_version);
+SDT_STATIC_ASSERT(sizeof(int32_t) == 4 && sizeof(float) == 4 && sizeof(double) == 8 && sizeof(void*) == 8, lp64_scalars);
+/* 17 int32_t scalars, then dy, dx, wt of SDT_MAX_TAPS int32_t each */
+SDT_STATIC_ASSERT(sizeof(sdt_conv_geom) == (17 + 3 * SDT_MAX_TAPS) * sizeof(int32_t), conv_geom_size);
+SDT_STATIC_ASSERT(offsetof(sdt_conv_geom, dy) == 17 * sizeof(int32_t), conv_geom_dy);
+SDT_STATIC_ASSERT(offsetof(sdt_conv_geom, wt) == (17 + 2 * SDT_MAX_TAPS) * sizeof(int32_t), conv_geom_wt);
+/* six pointers, float slope, int32_t groups */
+SDT_STATIC_ASSERT(sizeof(sdt_norm_bwd) == 6 * sizeof(void*) + sizeof(float) + sizeof(int32_t), norm_bwd_size);
+SDT_STATIC_ASSERT(offsetof(sdt_norm_bwd, slope) == 6 * sizeof(void*), norm_bwd_slope);
+SDT_STATIC_ASSERT(offsetof(sdt_norm_bwd, groups) == 6 * sizeof(void*) + sizeof(float), norm_bwd_groups);
+/* four pointers, six int32_t */
+SDT_STATIC_ASSERT(sizeof(sdt_wt_desc) == 4 * sizeof(void*) + 6 * sizeof(int32_t), wt_desc_size);
+SDT_STATIC_ASSERT(offsetof(sdt_wt_desc, cout) == 4 * sizeof(void*), wt_desc_cout);
+SDT_STATIC_ASSERT(offsetof(sdt_wt_desc, planes) == 4 * sizeof(void*) + 4 * sizeof(int32_t), wt_desc_planes);
+/* ten int32_t (an even number: the pointers behind them need no padding), six pointers */
+SDT_STATIC_ASSERT(sizeof(sdt_chain1d_layer) == 10 * sizeof(int32_t) + 6 * sizeof(void*), chain1d_layer_size);
+SDT_STATIC_ASSERT(offsetof(sdt_chain1d_layer, in_mode) == 6 * sizeof(int32_t), chain1d_layer_in_mode);
+SDT_STATIC_ASSERT(offsetof(sdt_chain1d_layer, w) == 10 * sizeof(int32_t), chain1d_layer_w);
+SDT_STATIC_ASSERT(offsetof(sdt_chain1d_layer, dx) == 10 * sizeof(int32_t) + 5 * sizeof(void*), chain1d_layer_dx);
+/* int64_t, three double, four int32_t */
+SDT_STATIC_ASSERT(sizeof(sdt_render_instance) == sizeof(int64_t) + 3 * sizeof(double) + 4 * sizeof(int32_t), render_instance_size);
+SDT_STATIC_ASSERT(offsetof(sdt_render_instance, shift_x) == sizeof(int64_t) + 3 * sizeof(double), render_instance_shift_x);
 
 int main(void) {
     sdt_conv_geom g;
     int rc;
     memset(&g, 0, sizeof g);
-    if (sdt_abi_version() != 5) return 10;
+    if (sdt_abi_version() != 5 || sdt_abi_version() != SDT_ABI_VERSION) return 10;
     if (sizeof(sdt_conv_geom) != (17 + 3 * SDT_MAX_TAPS) * sizeof(int32_t)) return 11;
     if (sizeof(sdt_wt_desc) != 4 * sizeof(void*) + 6 * sizeof(int32_t)) return 12;
     rc = sdt_conv_taps_f32(NULL, NULL, NULL, NULL, &g, NULL); /* zero geometry -> argument error, message set */

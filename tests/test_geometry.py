@@ -154,6 +154,12 @@ def test_library_exports_every_declared_symbol():
              "sdt_convsk_workspace_bytes", "sdt_convsk_dw_plan_bytes", "sdt_convsk_dw_workspace_bytes", "sdt_convsk_plan_bytes_t",
              "sdt_convsk_dw_plan_bytes_t", "sdt_convsk_get_spin_limit", "sdt_conv_dw_group_plan_bytes"}
     declared |= set(re.findall(r"^\s*(?:int64_t|unsigned)\s+(sdt_\w+)\s*\(", hdr, flags=re.M))
+    # the four patterns above know four return types: the header's parser (tests/test_abi_contract_host.py) reads ANY declaration, so a
+    # prototype with another return type, or one the patterns skip for its layout, does not escape the checks below
+    from test_abi_contract_host import Header
+    parsed = Header(hdr)
+    assert parsed.unparsed == [], parsed.unparsed
+    assert declared == set(parsed.names()), "prototypes the return-type patterns miss: %s" % sorted(declared ^ set(parsed.names()))
     for name in sorted(declared):
         assert hasattr(lib, name), "libsdt_hip.so does not export %s" % name
     assert declared - extra == set(_lib.SIGNATURES), "ctypes signatures out of sync with the header: %s" % ((declared - extra) ^ set(_lib.SIGNATURES))
